@@ -85,6 +85,9 @@ def parse_args():
                     help="launch path only (CPU test of --gpus N): the ranks rendezvous over gloo, barrier, max-reduce, rank 0 prints a stub line")
     ap.add_argument("--sharded-timeout", type=float, default=240.0, help="seconds the sharded flavour may take before the line is printed without it")
     ap.add_argument("--rank-timeout", type=float, default=1500.0, help="seconds after which the self-started ranks are stopped")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed windows, write what the last one computed (rank 0) as DIR/<name>.npy: the frame log of the timed "
+                         "steps, the final pose and the map (a fixed sample of it when it exceeds the size cap)")
     return ap.parse_args()
 
 
@@ -176,6 +179,39 @@ def quat_to_R(q):
     return np.array([[1 - (ty * y + tz * z), ty * x - tz * w, tz * x + ty * w],
                      [ty * x + tz * w, 1 - (tx * x + tz * z), tz * y - tx * w],
                      [tz * x - ty * w, tz * y + tx * w, 1 - (tx * x + ty * y)]], np.float32)
+
+
+DUMP_BYTES = 64 << 20        # --dump-outputs: cap on all files together
+
+
+def dump_outputs(out_dir, g, timed):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float32 / float64 .npy files.
+      frame_log    float32 [K, 10]  per timed step: pose7 (t, q), converged, passes, n_hit (gsdf_read_frame_log)
+      pose         float32 [7]      the tracker's pose after the last step (gsdf_get_pose)
+      map_keys     float64 [n, 3]   voxel keys of the map (gsdf_export, sorted by (z, y, x))
+      map_payload  float32 [n, 5]   dist, grad (3), weight of those voxels
+      map_count    float64 [1]      voxels in the whole map
+    A map larger than the cap is sampled by key: the voxels with the smallest values of a fixed, seeded hash of (x, y, z), so
+    that two builds that hold the same voxels write the same sample."""
+    os.makedirs(out_dir, exist_ok=True)
+    pose = np.asarray(g.get_pose(), np.float32)
+    keys, pay = g.export(sorted=True)
+    per_voxel = 3 * 8 + 5 * 4
+    cap = max(0, (DUMP_BYTES - timed.nbytes - pose.nbytes - 4096) // per_voxel)
+    if len(keys) > cap:
+        mult = np.random.default_rng(12345).integers(1, 1 << 62, size=3, dtype=np.uint64) | np.uint64(1)
+        with np.errstate(over="ignore"):
+            h = (keys.astype(np.int64).view(np.uint64) * mult).sum(axis=1, dtype=np.uint64)
+            h ^= h >> np.uint64(29)
+            h *= np.uint64(0xBF58476D1CE4E5B9)
+            h ^= h >> np.uint64(32)
+        pick = np.sort(np.lexsort((np.arange(len(h)), h))[:cap])       # ties broken by position: still deterministic
+        keys, pay = keys[pick], pay[pick]
+    np.save(os.path.join(out_dir, "frame_log.npy"), np.ascontiguousarray(timed, np.float32))
+    np.save(os.path.join(out_dir, "pose.npy"), pose)
+    np.save(os.path.join(out_dir, "map_keys.npy"), keys.astype(np.float64))
+    np.save(os.path.join(out_dir, "map_payload.npy"), np.ascontiguousarray(pay, np.float32))
+    np.save(os.path.join(out_dir, "map_count.npy"), np.array([g.count()], np.float64))
 
 
 def main():
@@ -338,6 +374,8 @@ def main():
     n_upd_timed = st["n_upd"] - st_w["n_upd"]
     n_hit_timed = st["n_hit"] - st_w["n_hit"]
     voxels = g.count()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, g, timed)
 
     # ---- staging-inclusive flavour: the same K frames, but every timed frame starts in a page-locked HOST buffer ----
     # main_scan_3d.cpp:213: the reference's loop loads the frame inside the loop.  Here: gsdf_dev_upload_ahead (the copy runs on

@@ -6,7 +6,7 @@
  * ncclFloat32 and ncclUint32 on the context's stream, the header / token / agree() scheme around them) never ran with peers.
  * libgsdf.so resolves the nccl* entry points with dlsym(RTLD_DEFAULT, ...) from whatever the process already holds
  * (gsdf_merge.hip:50-73); with LD_PRELOAD=tests/libfake_rccl.so that is THIS file: the seven entry points libgsdf uses,
- * implemented for N processes that share device 0.  tests/test_parallel.py starts 2 and 8 such processes which call
+ * implemented for N processes that share device 0.  tests/test_parallel.py starts 2 and 4 such processes which call
  * gsdf_merge_allreduce(ctx, comm) ITSELF.
  *
  * Mechanism: a POSIX shared-memory segment per communicator (name carried in the ncclUniqueId): a header with a sense-reversing

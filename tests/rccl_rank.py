@@ -49,7 +49,7 @@ def main():
     # smaller ones up first (the ranks learn the largest capacity from the header all-gather and agree that growing worked)
     g = pkg.GradSdf(vs, np.float32(TRUNC) * vs, W, H, seq.K, capacity_log2=18 + (1 if rank == world - 1 else 0), device=0)
     g.enable_vis(32)
-    lo, hi = pkg.parallel.shard_range(N_FRAMES, rank, world)  # uneven: 19 frames over 8 ranks = 3 / 2 per rank
+    lo, hi = pkg.parallel.shard_range(N_FRAMES, rank, world)  # uneven: 19 frames over 4 ranks = 5 / 4 per rank
     dev = [g.upload(seq.frame(i)[0]) for i in range(lo, hi)]
     for j, i in enumerate(range(lo, hi)):
         g.update_dev(dev[j], seq.frame(i)[1], seq.frame(i)[2])

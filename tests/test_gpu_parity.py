@@ -1336,7 +1336,7 @@ def test_closing_head_inside_the_fusion_launch_is_invisible(pkg, O, monkeypatch)
 
 @pytest.mark.gpu
 def test_no_frame_is_lost_when_contexts_share_the_gpu(pkg, O):
-    """Round 6, found by test_bench_gpus_8_end_to_end_over_the_rccl_double (1 run in 3): in a k_fuse<.., HEAD> launch a workgroup of a
+    """Round 6, found by the eight-rank form of test_bench_gpus_4_end_to_end_over_the_rccl_double (1 run in 3): in a k_fuse<.., HEAD> launch a workgroup of a
     later dispatch round could take the solver's sticky `done` word (fresh) for "optimize() ended before this launch" and then use a
     STALE st->done = 0 from its XCD's L2 -- it left without fusing its tile and without its ticket, so the launch had no last
     workgroup: no frame-log row, the deferred list never added.  The window opens when lines of the state block are evicted between
