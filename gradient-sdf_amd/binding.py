@@ -34,7 +34,8 @@ class GsdfError(RuntimeError):
 class Stats(C.Structure):
     _fields_ = [("n_upd", C.c_int64), ("n_valid", C.c_int64), ("n_hit", C.c_int64),
                 ("track_passes", C.c_int32), ("converged", C.c_int32), ("frames", C.c_int64),
-                ("n_deferred", C.c_int64), ("fuse_timeouts", C.c_int64)]
+                ("n_deferred", C.c_int64), ("fuse_timeouts", C.c_int64), ("far_tiles", C.c_int64), ("fuse_blocks", C.c_int64),
+                ("fuse_launches", C.c_int64), ("far_table_launches", C.c_int64)]
 
 
 def build(force=False):
@@ -301,6 +302,10 @@ class GradSdf:
 
     def reset(self):
         self._chk(self.L.gsdf_reset(self.h))
+
+    def set_zrange(self, zmin, zmax):
+        """Sdf::set_zmin / set_zmax (Sdf.h:123-129): the depth range of later fusions and tracker passes"""
+        self._chk(self.L.gsdf_set_zrange(self.h, np.float32(zmin), np.float32(zmax)))
 
     def debug_flags(self, flags):
         """Path-forcing / measurement switches; exists only in the test build (lib=load_test_lib())."""

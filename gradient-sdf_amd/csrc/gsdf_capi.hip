@@ -187,10 +187,12 @@ static uint32_t* stats_of(const gsdf_ctx* c, const float* nrm) {
 
 /* one k_fuse launch: depth + its normal planes `nrm` (3 x N floats) -> the map.  next_depth (nullable): the launch's extra
  * workgroups compute the normals of that frame into next_nrm */
-int launch_fuse(gsdf_ctx* c, const float* depth_dev, const float* nrm, const gsdf_pose_arg& pose, int use_dev_pose,
+int launch_fuse(gsdf_ctx* c, const float* depth_dev, const float* nrm, const gsdf_pose_arg& pose, int use_dev_pose, int far_table,
                 const float* next_depth, float* next_nrm, const gsdf_fuse_head* head = nullptr, unsigned int next_token = 0u) {
     const size_t N = (size_t)c->W * c->H;
     c->occ_dirty = true;                                      /* new blocks: the raycaster's filters are rebuilt when it next runs */
+    c->fuse_launches += 1;
+    c->far_table_launches += far_table ? 1 : 0;
     {
         prof_scope ps(c, 1);
         c->fuse_tag += 1;
@@ -205,8 +207,9 @@ int launch_fuse(gsdf_ctx* c, const float* depth_dev, const float* nrm, const gsd
                          /* long deferred lists lately (the note lags by a launch or two: a hint, not a condition) */
                          c->progress && c->progress[2] > 8192u ? 1 : 0, c->progress ? c->progress_dev + 2 : nullptr,
                          /* many tiles did not fit the small LDS table lately (far geometry): the kernel with the larger one.
-                          * Like the note above a hint that lags by a launch or two, never a condition for correctness. */
-                         fuse_far_table(c), head,
+                          * Like the note above a hint that lags by a launch or two, never a condition for correctness; the
+                          * caller read it once for the whole frame entry (fuse_far_table) */
+                         far_table, head,
                          next_depth, next_nrm, next_nrm ? next_nrm + N : nullptr, next_nrm ? next_nrm + 2 * N : nullptr, c->win,
                          stats_of(c, nrm), next_nrm ? stats_of(c, next_nrm) : nullptr, next_token);
     }
@@ -216,7 +219,7 @@ int launch_fuse(gsdf_ctx* c, const float* depth_dev, const float* nrm, const gsd
 }
 
 /* normals (unless the frame's were computed beside its first tracker pass: normals_done) + fusion, in stream order */
-int enqueue_fuse(gsdf_ctx* c, const float* depth_dev, const gsdf_pose_arg& pose, int use_dev_pose, bool normals_done, int set,
+int enqueue_fuse(gsdf_ctx* c, const float* depth_dev, const gsdf_pose_arg& pose, int use_dev_pose, int far_table, bool normals_done, int set,
                  const float* next_depth, const gsdf_fuse_head* head, int next_set, unsigned int next_token) {
     const size_t N = (size_t)c->W * c->H;
     /* tracked frames: set 2, filled beside the first tracker passes -- or the set the PREVIOUS frame's fusion filled in its
@@ -233,7 +236,7 @@ int enqueue_fuse(gsdf_ctx* c, const float* depth_dev, const gsdf_pose_arg& pose,
     /* gsdf_hint_next_depth_dev: the launch's last workgroups compute NormalEstimator::compute of the NEXT frame into set
      * next_set -- if the launch's gate is open -- and leave next_token in st->nrm_token */
     float* next_nrm = next_depth ? c->normals + (size_t)next_set * 3 * N : nullptr;
-    return launch_fuse(c, depth_dev, nrm, pose, use_dev_pose, next_depth, next_nrm, head, next_token);
+    return launch_fuse(c, depth_dev, nrm, pose, use_dev_pose, far_table, next_depth, next_nrm, head, next_token);
 }
 
 /* RigidPointOptimizer::optimize_sampled as a chain of per-pass launches.  The convergence test, the pose update
@@ -247,7 +250,7 @@ int enqueue_fuse(gsdf_ctx* c, const float* depth_dev, const gsdf_pose_arg& pose,
  * done, passes) and only issues a further batch if the optimisation has not ended by the last head of the
  * previous one.  Correctness never depends on what the host sees: a late or lost observation only costs empty
  * launches. */
-int enqueue_fuse(gsdf_ctx* c, const float* depth_dev, const gsdf_pose_arg& pose, int use_dev_pose, bool normals_done, int set = 2,
+int enqueue_fuse(gsdf_ctx* c, const float* depth_dev, const gsdf_pose_arg& pose, int use_dev_pose, int far_table, bool normals_done, int set = 2,
                  const float* next_depth = nullptr, const gsdf_fuse_head* head = nullptr, int next_set = 0, unsigned int next_token = 0u);
 
 /* 1 = optimize() ended, 0 = the head of launch `last` ran and it has not ended, -1 = gave up waiting */
@@ -301,8 +304,11 @@ int enqueue_track(gsdf_ctx* c, const float* depth_dev, int iters, float conv, fl
         if ((w >> 16) == c->prev_track_serial && (w & 0x8000u)) c->prev_slow = (int)(w & 0x7FFFu) > c->prev_first_last;
     }
     /* ... and not while the fusion uses the larger LDS table (far geometry): that instantiation with the normals role is at the
-     * register limit and moves its records unpaired, with the head it spills -- both cost more than the step saves */
-    const bool new_route = fuse_after && !c->profiling && iters > 0 && !c->prev_slow && !fuse_far_table(c);
+     * register limit and moves its records unpaired, with the head it spills -- both cost more than the step saves.  The choice is
+     * read ONCE here and handed to every fusion launch of this frame: the word it comes from is written by the device while the
+     * host runs, and a second read could pick the larger table for a launch that carries the normals role or the head. */
+    const int far = fuse_far_table(c);
+    const bool new_route = fuse_after && !c->profiling && iters > 0 && !c->prev_slow && !far;
     const float* hint = new_route ? c->hint_next : nullptr;
     c->nrm_ready_depth = nullptr;        /* consumed (or not ours) */
     c->hint_next = nullptr;
@@ -317,7 +323,7 @@ int enqueue_track(gsdf_ctx* c, const float* depth_dev, int iters, float conv, fl
     }
     if (iters <= 0) {
         gsdf_launch_track_none(c->stream, c->st);
-        return fuse_after ? enqueue_fuse(c, depth_dev, unused, 1, false) : GSDF_OK;
+        return fuse_after ? enqueue_fuse(c, depth_dev, unused, 1, far, false) : GSDF_OK;
     }
     if (iters > 0x7FFF) return fail(GSDF_ERR_INVALID, "num_iterations must be <= 32767");
     gsdf_normals_job nj;
@@ -360,7 +366,7 @@ int enqueue_track(gsdf_ctx* c, const float* depth_dev, int iters, float conv, fl
                                   fuse_after ? &nj : nullptr);
         }
         if (fuse_after) {
-            const int rc = enqueue_fuse(c, depth_dev, unused, 1, true, fuse_set, hint, nullptr, next_set, next_token);   /* main_scan_3d.cpp:261-265 */
+            const int rc = enqueue_fuse(c, depth_dev, unused, 1, far, true, fuse_set, hint, nullptr, next_set, next_token);   /* main_scan_3d.cpp:261-265 */
             if (rc) return rc;
         }
         hipError_t e = hipGetLastError();
@@ -419,7 +425,7 @@ int enqueue_track(gsdf_ctx* c, const float* depth_dev, int iters, float conv, fl
                 hd.conv_sq = tp.conv_sq; hd.damping = tp.damping; hd.max_passes = tp.max_passes;
                 hd.serial = tp.serial; hd.progress = tp.progress; hd.rows = c->partials; hd.debug = tp.debug;
             }
-            const int rc = enqueue_fuse(c, depth_dev, unused, 1, true, fuse_set, hint, stand_in ? &hd : nullptr, next_set, next_token);   /* main_scan_3d.cpp:261-265 */
+            const int rc = enqueue_fuse(c, depth_dev, unused, 1, far, true, fuse_set, hint, stand_in ? &hd : nullptr, next_set, next_token);   /* main_scan_3d.cpp:261-265 */
             if (rc) return rc;
             fuse_queued = true;
         }
@@ -435,7 +441,7 @@ int enqueue_track(gsdf_ctx* c, const float* depth_dev, int iters, float conv, fl
         }
         if (ended) {
             if (fuse_after && !fuse_queued) {
-                const int rc = enqueue_fuse(c, depth_dev, unused, 1, true, fuse_set, hint, nullptr, next_set, next_token);
+                const int rc = enqueue_fuse(c, depth_dev, unused, 1, far, true, fuse_set, hint, nullptr, next_set, next_token);
                 if (rc) return rc;
             }
             break;
@@ -462,7 +468,7 @@ int gsdf_flush_pending(gsdf_ctx* c) {
     c->pending.valid = false;
     if (hipSetDevice(c->device) != hipSuccess) return fail(GSDF_ERR_HIP, "hipSetDevice");
     const size_t N = (size_t)c->W * c->H;
-    return launch_fuse(c, c->pending.depth, c->normals + (size_t)c->pending.set * 3 * N, c->pending.pose, 0, nullptr, nullptr);
+    return launch_fuse(c, c->pending.depth, c->normals + (size_t)c->pending.set * 3 * N, c->pending.pose, 0, fuse_far_table(c), nullptr, nullptr);
 }
 #define GSDF_FLUSH(c) do { if ((c) && (c)->pending.valid) { const int rc_ = gsdf_flush_pending(c); if (rc_) return rc_; } } while (0)
 /* The staging entries (gsdf_dev_upload*) write device memory the caller names.  A GT-pose fusion that still waits for its
@@ -692,6 +698,7 @@ int gsdf_reset(gsdf_ctx* c) {
     if (!c) return fail(GSDF_ERR_INVALID, "null context");
     HIP_TRY(hipSetDevice(c->device));
     c->pending.valid = false;                              /* a fusion that was never launched is dropped with the map */
+    c->fuse_launches = 0; c->far_table_launches = 0;
     c->hint_next = nullptr; c->nrm_ready_depth = nullptr;  /* (gsdf_hint_next_depth_dev: a new scan starts without them) */
     c->prev_track_serial = 0; c->prev_slow = false;
     if (c->deferred_count) HIP_TRY(hipMemsetAsync(c->deferred_count, 0, sizeof(unsigned int), c->stream));
@@ -739,6 +746,13 @@ int gsdf_capacity(gsdf_ctx* c, int* capacity_log2) {
 int gsdf_set_zrange(gsdf_ctx* c, float zmin, float zmax) {
     GSDF_FLUSH(c);
     if (!c) return fail(GSDF_ERR_INVALID, "null context");
+    if (!std::isfinite(zmin) || !std::isfinite(zmax) || !(zmax > zmin))
+        return fail(GSDF_ERR_INVALID, "gsdf_set_zrange: finite zmin < zmax required");
+    if (zmin != c->zmin || zmax != c->zmax) {
+        /* the tile statistics of normals computed ahead (gsdf_hint_next_depth_dev) were taken under the old range: a tile with no
+         * pixel inside it would count no valid pixel and never be walked.  Forget them; the next frame computes its own. */
+        c->hint_next = nullptr; c->nrm_ready_depth = nullptr;
+    }
     c->zmin = zmin; c->zmax = zmax;
     return GSDF_OK;
 }
@@ -853,7 +867,7 @@ int gsdf_update_dev(gsdf_ctx* c, const float* depth_dev, const float R[9], const
     if (!c->defer || c->profiling) {                       /* event-timed replays: normals and fusion as two launches, in order */
         int rc = gsdf_flush_pending(c);
         if (rc) return rc;
-        return enqueue_fuse(c, depth_dev, pose, 0, false);
+        return enqueue_fuse(c, depth_dev, pose, 0, fuse_far_table(c), false);
     }
     /* MapGradPixelSdf.cpp:60: the normals of a frame depend on its depth only.  A run of GT-pose fusions (the branch
      * main_scan_3d.cpp:250-254; frame-sharded fusion) is pipelined by ONE call: the k_fuse of frame i is launched when frame
@@ -872,7 +886,7 @@ int gsdf_update_dev(gsdf_ctx* c, const float* depth_dev, const float R[9], const
         HIP_TRY(hipGetLastError());
     } else {
         const float* pn = c->normals + (size_t)c->pending.set * 3 * N;
-        int rc = launch_fuse(c, c->pending.depth, pn, c->pending.pose, 0, depth_dev, nrm);
+        int rc = launch_fuse(c, c->pending.depth, pn, c->pending.pose, 0, fuse_far_table(c), depth_dev, nrm);
         c->pending.valid = false;
         if (rc) return rc;
     }
@@ -1023,6 +1037,10 @@ int gsdf_get_stats(gsdf_ctx* c, gsdf_stats* out) {
     out->frames = s.frames;
     out->n_deferred = (int64_t)s.n_deferred;
     out->fuse_timeouts = (int64_t)s.fuse_timeouts;
+    out->far_tiles = c->progress ? (int64_t)c->progress[3] : 0;
+    out->fuse_blocks = c->fuse_blocks;
+    out->fuse_launches = c->fuse_launches;
+    out->far_table_launches = c->far_table_launches;
     return GSDF_OK;
 }
 
@@ -1647,6 +1665,19 @@ int gsdf_dev_free(gsdf_ctx* c, void* dev_ptr) {
     if (!c) return fail(GSDF_ERR_INVALID, "null context");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    if (dev_ptr) {
+        /* a hinted frame or one whose normals were computed ahead (gsdf_hint_next_depth_dev) inside the freed allocation: the
+         * allocator may hand the same address out again with other contents, which the normals would not belong to */
+        size_t bytes = 0;
+        void* base = nullptr;
+        if (hipMemGetAddressRange((hipDeviceptr_t*)&base, &bytes, (hipDeviceptr_t)dev_ptr) != hipSuccess || !base) {
+            (void)hipGetLastError();
+            base = dev_ptr; bytes = 1;
+        }
+        const uintptr_t a0 = (uintptr_t)base, a1 = a0 + bytes;
+        for (const float** q : { &c->nrm_ready_depth, &c->hint_next })
+            if (*q && (uintptr_t)*q >= a0 && (uintptr_t)*q < a1) *q = nullptr;
+    }
     HIP_TRY(hipFree(dev_ptr));
     return GSDF_OK;
 }

@@ -133,6 +133,7 @@ struct gsdf_ctx {
     unsigned int* progress_dev = nullptr;
     int adaptive = 1;                              /* issue tracker passes in batches, following the device (see enqueue_track) */
     int far_table = -1;                            /* fusion kernel's LDS table: -1 chosen per launch from the previous fusions, 0 / 1 pinned */
+    long long fuse_launches = 0, far_table_launches = 0; /* fusion launches since create/reset, and those with the larger table (gsdf_get_stats) */
     int first_batch = 5, next_batch = 8;           /* launches per batch: 5 cover the usual <= 4 passes + their last head; a frame that needs
                                                       more is most likely one that runs all 25 (pass counts on the bench stream: 142 x <= 6, 7 x 7..22,
                                                       51 x 25) -- batches of 8 behind the first: 6 656 -> 6 815 frames/s on the default window (4 / 12 / 21: 6 656 / 6 780 / 6 760) */

@@ -54,6 +54,11 @@ typedef struct gsdf_stats {
     int64_t n_deferred;   /* voxel contributions that took the deferred (float-atomic) route of the fusion flush
                              since create/reset: near tiles, LDS overflow, timed-out waits (0 in steady state)  */
     int64_t fuse_timeouts;/* fusion tiles whose bounded wait for a neighbouring tile expired (they deferred)     */
+    int64_t far_tiles;    /* tiles of the last fusion that did not fit the small LDS table in one band; while more than
+                             fuse_blocks / 16 of them, the frame entries choose the fusion kernel with the larger table  */
+    int64_t fuse_blocks;  /* fusion tiles of a frame                                                             */
+    int64_t fuse_launches;      /* fusion launches since create/reset (a tracked frame queues one per batch)        */
+    int64_t far_table_launches; /* of those, the ones with the larger LDS table                                     */
 } gsdf_stats;
 
 const char* gsdf_last_error(void);
@@ -86,7 +91,9 @@ int gsdf_grow(gsdf_ctx* c, int new_capacity_log2);
 int gsdf_set_auto_grow(gsdf_ctx* c, int max_capacity_log2);
 int gsdf_capacity(gsdf_ctx* c, int* capacity_log2);
 
-/* Sdf::set_zmin / Sdf::set_zmax -- Sdf.h:123-129 (defaults 0.5 / 3.5) */
+/* Sdf::set_zmin / Sdf::set_zmax -- Sdf.h:123-129 (defaults 0.5 / 3.5).  Both bounds finite and zmin < zmax, else
+ * GSDF_ERR_INVALID and the range stays as it was.  A change of range withdraws a next-frame hint (gsdf_hint_next_depth_dev):
+ * normals computed ahead carry tile statistics taken under the old range. */
 int gsdf_set_zrange(gsdf_ctx* c, float zmin, float zmax);
 
 /* new cv::NormalEstimator<float>(W, H, K, Size(win,win)) -> cache() -- normals/NormalEstimator.h:81-165,
@@ -147,10 +154,12 @@ int gsdf_track_and_fuse_dev(gsdf_ctx* c, const float* depth_dev, const float K[9
  * frame converged; it leaves a token, and the next frame's tracker launches, which carry the normals tiles as ever, skip them
  * when they find it.  The same launch also performs the closing head of the current frame's optimize() (reduce, solve, stop
  * test of the first batch's last pass) instead of a tracker launch of its own.
- * The normals depend on the depth image alone (MapGradPixelSdf.cpp:60), so results do not: same poses, same map
- * (tests/test_gpu_parity.py::test_next_depth_hint_is_invisible_except_in_time).  Contract: next_depth_dev already holds the
- * next frame when the CURRENT frame's gsdf_track_and_fuse_dev is called, and stays unchanged until the next frame's call; a copy
- * into it through gsdf_dev_upload* in between withdraws the hint, as does any other frame entry; a hint that does not match the
+ * The normals and the fusion's tile statistics depend on the depth image and the depth range alone (MapGradPixelSdf.cpp:60,
+ * gsdf_set_zrange), so results do not: same poses, same map (tests/test_gpu_parity.py::
+ * test_next_depth_hint_is_invisible_except_in_time).  Contract: next_depth_dev already holds the next frame when the CURRENT
+ * frame's gsdf_track_and_fuse_dev is called, and stays unchanged until the next frame's call; a copy into it through
+ * gsdf_dev_upload* in between withdraws the hint, as do a gsdf_dev_free of its allocation, a gsdf_set_zrange that changes the
+ * range, and any other frame entry; a hint that does not match the
  * next call's depth_dev is ignored.  One hint per frame; NULL withdraws it.  No device work, never an error for a mismatch. */
 int gsdf_hint_next_depth_dev(gsdf_ctx* c, const float* next_depth_dev);
 /* both in one call: gsdf_hint_next_depth_dev(c, next_depth_dev) + gsdf_track_and_fuse_dev(c, depth_dev, ...) -- for hosts whose
@@ -330,7 +339,7 @@ int gsdf_extract_mesh(gsdf_ctx* c, float iso, const int8_t tri_table[256 * 16], 
 
 /* device-memory plumbing so callers can stage frames in HBM without another runtime */
 int gsdf_dev_alloc(gsdf_ctx* c, void** dev_ptr, int64_t bytes);
-int gsdf_dev_free(gsdf_ctx* c, void* dev_ptr);
+int gsdf_dev_free(gsdf_ctx* c, void* dev_ptr);          /* withdraws a next-frame hint that lies in the freed allocation */
 int gsdf_dev_upload(gsdf_ctx* c, void* dev_dst, const void* host_src, int64_t bytes);
 int gsdf_dev_download(gsdf_ctx* c, void* host_dst, const void* dev_src, int64_t bytes);
 /* Asynchronous frame staging for a host loop that keeps the GPU fed (the Scan3D CLI): page-locked host

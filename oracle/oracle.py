@@ -102,6 +102,10 @@ class Oracle:
             self.L.gsdfo_destroy(self.h)
             self.h = None
 
+    def set_zrange(self, zmin, zmax):
+        """Sdf::set_zmin / set_zmax (Sdf.h:123-129)"""
+        self.L.gsdfo_set_zrange(self.h, np.float32(zmin), np.float32(zmax))
+
     def set_threads(self, threads):
         """Threads of the OMP-structured variants (update(omp=True), track(omp=True))."""
         self.L.gsdfo_set_threads(self.h, int(threads))

@@ -27,7 +27,9 @@ def _mk(pkg, O, kind="spheres", W=160, H=120, vs=0.02, trunc=5, cap=18, seed=1, 
     return seq, g, o
 
 
-def _cmp_tables(g, o, weight_scale=1.0):
+def _cmp_tables(g, o, weight_scale=1.0, exclusion=None):
+    """the parity bar on two maps; returns the voxel count.  exclusion (a dict, optional) receives what the direction rule below
+    leaves out: the fraction of voxels it excludes and the largest direction error among the excluded ones with |grad| > 0"""
     kg, pg = g.export(sorted=True)
     ko, po = o.export()
     assert kg.shape == ko.shape, (kg.shape, ko.shape)
@@ -47,6 +49,12 @@ def _cmp_tables(g, o, weight_scale=1.0):
     # which is what these directions feed, is held to 1e-4 by its own tests).
     ng, no = np.linalg.norm(pg[:, 1:4], axis=1), np.linalg.norm(po[:, 1:4], axis=1)
     ok = no >= np.maximum(1e-2 * po[:, 4], 0.05)
+    out = ~ok & (no > 0) & (ng > 0)
+    err_out = float(np.abs(pg[out, 1:4] / ng[out, None] - po[out, 1:4] / no[out, None]).max()) if out.any() else 0.0
+    print("MEASURED direction rule: %d of %d voxels excluded (%.4f), largest direction error among the excluded with |grad| > 0: %.3e"
+          % (int((~ok).sum()), ok.size, float(1.0 - ok.mean()), err_out))
+    if exclusion is not None:
+        exclusion.update(fraction=float(1.0 - ok.mean()), max_dir_err=err_out, n=int(ok.size))
     assert ok.mean() > 0.95
     assert np.abs(pg[ok, 1:4] / ng[ok, None] - po[ok, 1:4] / no[ok, None]).max() <= TOL
     return kg.shape[0]
@@ -506,7 +514,7 @@ def test_raycast_matches_definition_and_input_depth(pkg, O):
     g.close()
 
 
-def test_argument_errors_of_the_newer_entries(pkg):
+def test_argument_errors_of_the_newer_entries(pkg, O):
     """Error behaviour of entries added after the first ABI: bad arguments are reported, nothing crashes."""
     import ctypes as C
     L = pkg.binding.load()
@@ -519,6 +527,24 @@ def test_argument_errors_of_the_newer_entries(pkg):
     assert (z == 0).all() and (n == 0).all()
     st = g.stats()
     assert st["n_deferred"] == 0 and st["fuse_timeouts"] == 0
+    # gsdf_set_zrange: a non-finite bound or zmax <= zmin is rejected and the range stays as it was (checked by a fusion below)
+    g.set_zrange(1.0, 2.0)                                    # a valid change is accepted
+    for zmin, zmax in ((np.nan, 2.0), (1.0, np.nan), (-np.inf, 2.0), (1.0, np.inf), (2.0, 1.0), (1.5, 1.5)):
+        with pytest.raises(pkg.binding.GsdfError) as e:
+            g.set_zrange(zmin, zmax)
+        assert e.value.code == pkg.binding.ERR_INVALID
+    g.close()
+    seq = pkg.synth.Sequence("spheres", 64, 48, n_frames=1, seed=1)
+    g = pkg.GradSdf(np.float32(0.02), np.float32(0.1), 64, 48, seq.K, capacity_log2=14, zmin=1.8, zmax=2.2)
+    with pytest.raises(pkg.binding.GsdfError):
+        g.set_zrange(2.0, 1.0)
+    o = O.Oracle(np.float32(0.02), np.float32(0.1), 64, 48, seq.K, zmin=1.8, zmax=2.2)
+    d, R, t = seq.frame(0)
+    assert ((d > 0.5) & (d <= 1.8)).any() and ((d >= 2.2) & (d < 3.5)).any()    # the premise: (1.8, 2.2) cuts at both ends here
+    g.update(d, R, t)
+    nu, nv = o.update(d, R, t)
+    st = g.stats()
+    assert st["n_upd"] == nu and st["n_valid"] == nv
     g.close()
 
 

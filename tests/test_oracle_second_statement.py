@@ -76,10 +76,10 @@ def std_round(x):
 class SecondStatement:
     """MapGradPixelSdf as the reference writes it: a dict of voxels with the RUNNING MEAN of the distance"""
 
-    def __init__(self, voxel_size, T):
+    def __init__(self, voxel_size, T, zmin=0.5, zmax=3.5):
         self.vs = f32(voxel_size); self.vs_inv = f32(1.0 / float(f32(voxel_size)))       # MapGradPixelSdf.h:99-103
         self.T = f32(T); self.inv_T = f32(1.0 / float(f32(T)))                            # Sdf.h:103-107
-        self.z_min, self.z_max = f32(0.5), f32(3.5)                                        # Sdf.h:67-68
+        self.z_min, self.z_max = f32(zmin), f32(zmax)                                      # Sdf.h:67-68 (set_zmin / set_zmax :123-129)
         self.tsdf = {}
         self.counter = 0
 
@@ -174,9 +174,10 @@ def tsdf_return(dist, unit, c):
     return f32(np.float64(dist) + np.float64(1.2) * np.float64(dot))
 
 
-def first_pass(st, depth, K, R, t):
+def first_pass(st, depth, K, R, t, damping=1.0):
     """RigidPointOptimizer::optimize_sampled, the sums of its first iteration -- RigidPointOptimizer.cpp:51-84 -- with
-    MapGradPixelSdf::weights / tsdf (MapGradPixelSdf.h:109-125) on the second statement's own voxel dict"""
+    MapGradPixelSdf::weights / tsdf (MapGradPixelSdf.h:109-125) on the second statement's own voxel dict, and its step
+    xi = damping_ * H.llt().solve(g) (:86; the solve in double here)"""
     K = K.astype(np.float32); R = R.astype(np.float32); t = t.astype(np.float32)
     fx_inv, fy_inv, cx, cy = f32(f32(1) / K[0, 0]), f32(f32(1) / K[1, 1]), K[0, 2], K[1, 2]
     E = f32(0); g = [f32(0)] * 6; Hm = [[f32(0)] * 6 for _ in range(6)]; count = 0
@@ -203,7 +204,8 @@ def first_pass(st, depth, K, R, t):
             g = [f32(g[i] + f32(phi * J[i])) for i in range(6)]
             Hm = [[f32(Hm[i][j] + f32(J[i] * J[j])) for j in range(6)] for i in range(6)]
             count += 1
-    return E, g, Hm, count
+    xi = np.float64(f32(damping)) * np.linalg.solve(np.array(Hm, np.float64), np.array(g, np.float64))
+    return E, g, Hm, count, xi
 
 
 def test_second_statement_of_the_first_tracker_pass(pkg, O):
@@ -221,13 +223,67 @@ def test_second_statement_of_the_first_tracker_pass(pkg, O):
     o.update(d0, Rq, t0)
     d1, _, _ = seq.frame(1)
     conv, pose, used, trace, hits = o.track(d1, p0, iters=1)
-    E, g, Hm, count = first_pass(st, d1, seq.K, Rq, t0)
+    E, g, Hm, count, xi = first_pass(st, d1, seq.K, Rq, t0)
     tr = trace[0]
     assert count == int(hits[0]) == int(tr[28]) > 500
     mine = np.array([E] + g + [Hm[i][j] for i in range(6) for j in range(i, 6)], np.float32)
     assert np.array_equal(mine.view(np.uint32), tr[:28].view(np.uint32))           # E, g, H: the same bits
-    xi = np.linalg.solve(np.array(Hm, np.float64), np.array(g, np.float64))        # H.llt().solve(g), in double
     assert np.abs(xi - tr[29:35]).max() <= 1e-3 * np.abs(xi).max()                 # (the float LLT of a 6x6 with condition ~1e4)
+
+
+def test_second_statement_at_a_non_default_range_and_damping(pkg, O):
+    """The same two statements -- fusion of two frames, then the first tracker pass -- with Sdf::set_zmin / set_zmax at (1.5, 2.2)
+    instead of (0.5, 3.5) -- the spheres in front and the back wall are cut -- and RigidOptimizer::set_damping(0.5) instead of 1: both gates (MapGradPixelSdf.cpp:87,
+    RigidPointOptimizer.cpp:64-65) must use the range that was set, and the step must carry the damping."""
+    W, H, win = 48, 36, 11
+    zmin, zmax, damping = 1.5, 2.2, 0.5
+    seq = pkg.synth.Sequence("tum", W, H, n_frames=3, seed=5)
+    vs, T = np.float32(0.04), np.float32(5) * np.float32(0.04)
+    o = O.Oracle(vs, T, W, H, seq.K)
+    o.set_zrange(zmin, zmax)
+    st = SecondStatement(vs, T, zmin, zmax)
+    oc = o.normals_cache()
+    frames = [seq.frame(i) for i in range(3)]
+    # the premise: the range cuts the frames at both ends (pixels below zmin and above zmax that the default range keeps)
+    d_all = np.stack([f[0] for f in frames])
+    assert ((d_all > 0.5) & (d_all <= zmin)).sum() > 50 and ((d_all >= zmax) & (d_all < 3.5)).sum() > 50
+    p0 = np.concatenate([frames[0][2], O.R_to_quat(frames[0][1])]).astype(np.float32)
+    Rq = O.quat_to_R(p0[3:])
+    for i in range(2):
+        d, R, t = frames[i]
+        if i == 0:
+            R = Rq
+        n_ref = o.normals(d)
+        st.update(d, oc[0], oc[1], oc[4], n_ref[0], n_ref[1], n_ref[2], R, t)
+        o.update(d, R, t)
+    keys, pay = o.export()
+    mine = sorted(st.tsdf.items(), key=lambda kv: (kv[0][2], kv[0][1], kv[0][0]))
+    assert len(mine) == len(keys) > 1000
+    assert np.array_equal(np.array([k for k, _ in mine], np.int32), keys)
+    mp = np.array([[v[0], v[1][0], v[1][1], v[1][2], v[2]] for _, v in mine], np.float32)
+    assert np.array_equal(mp.view(np.uint32), pay.view(np.uint32))
+    # and the map differs from the one the default range builds (the range is not a pass-through)
+    o_def = O.Oracle(vs, T, W, H, seq.K)
+    for i in range(2):
+        d, R, t = frames[i]
+        o_def.update(d, Rq if i == 0 else R, t)
+    assert o_def.count() > len(keys)
+    # the first tracker pass of frame 2 against that map, from frame 1's pose
+    _, R1, t1 = frames[1]
+    p1 = np.concatenate([t1, O.R_to_quat(R1)]).astype(np.float32)
+    R1q = O.quat_to_R(p1[3:])
+    d2 = frames[2][0]
+    conv, pose, used, trace, hits = o.track(d2, p1, iters=1, damping=damping)
+    E, g, Hm, count, xi = first_pass(st, d2, seq.K, R1q, t1, damping=damping)
+    tr = trace[0]
+    assert count == int(hits[0]) == int(tr[28]) > 100
+    mine = np.array([E] + g + [Hm[i][j] for i in range(6) for j in range(i, 6)], np.float32)
+    assert np.array_equal(mine.view(np.uint32), tr[:28].view(np.uint32))
+    assert np.abs(xi - tr[29:35]).max() <= 1e-3 * np.abs(xi).max()
+    # the step is damped: half of the undamped one (the oracle's trace at damping 1 from the same state)
+    _, _, _, trace1, _ = o.track(d2, p1, iters=1)
+    assert np.array_equal(trace1[0, :29].view(np.uint32), tr[:29].view(np.uint32))
+    assert np.abs(tr[29:35] - np.float32(damping) * trace1[0, 29:35]).max() <= 1e-7 * np.abs(trace1[0, 29:35]).max()
 
 
 # ---- PhotoBA: getEnergy, written once more from ps_optimizer/PhotometricOptimizer.cpp:57-77 (interpolateImage), :236-260
