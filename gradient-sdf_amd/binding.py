@@ -23,6 +23,7 @@ LIB_PATH = os.environ.get("GSDF_LIB", os.path.join(CSRC, "libgsdf.so"))   # GSDF
 TEST_LIB_PATH = os.environ.get("GSDF_TEST_LIB", os.path.join(CSRC, "libgsdf_test.so"))   # GSDF_TEST_LIB: variants of the test build (tools/)
 
 GSDF_OK, ERR_TABLE_FULL, ERR_KEY_RANGE, ERR_INVALID, ERR_HIP, ERR_NO_DEVICE = 0, 1, 2, 3, 4, 5
+MAP_GRAD, MAP_BASE = 0, 1                                     # gsdf_set_map_type (include/gsdf.h)
 
 
 class GsdfError(RuntimeError):
@@ -102,6 +103,8 @@ def load(path=None):
         "gsdf_destroy": (None, [vp]),
         "gsdf_reset": (C.c_int, [vp]),
         "gsdf_set_zrange": (C.c_int, [vp, C.c_float, C.c_float]),
+        "gsdf_set_map_type": (C.c_int, [vp, C.c_int]),
+        "gsdf_get_map_type": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "gsdf_normals_init": (C.c_int, [vp, C.c_int, C.c_int, fp, C.c_int]),
         "gsdf_normals_cache": (C.c_int, [vp, fp]),
         "gsdf_normals_compute": (C.c_int, [vp, fp, fp, fp, fp]),
@@ -184,6 +187,7 @@ def load(path=None):
 
 ABI_SYMBOLS = [
     "gsdf_last_error", "gsdf_version", "gsdf_create", "gsdf_destroy", "gsdf_reset", "gsdf_set_zrange",
+    "gsdf_set_map_type", "gsdf_get_map_type",
     "gsdf_normals_init", "gsdf_normals_cache", "gsdf_normals_compute", "gsdf_update", "gsdf_update_dev",
     "gsdf_track", "gsdf_track_sampled", "gsdf_hint_next_depth_dev", "gsdf_track_and_fuse_ahead_dev", "gsdf_set_pose", "gsdf_get_pose", "gsdf_track_and_fuse_dev", "gsdf_read_frame_log",
     "gsdf_sync", "gsdf_get_stats", "gsdf_count", "gsdf_export", "gsdf_enable_vis", "gsdf_export_vis",
@@ -242,10 +246,13 @@ def _fp(a):
 
 
 class GradSdf:
-    """MapGradPixelSdf + RigidPointOptimizer + NormalEstimator behind the C-ABI (one GPU)."""
+    """MapGradPixelSdf + RigidPointOptimizer + NormalEstimator behind the C-ABI (one GPU).
+
+    map_type=MAP_BASE makes the context a MapPixelSdf (the plain-SDF baseline, --scan-type base-sdf): same fusion, trilinear
+    query and tracker (include/gsdf.h, gsdf_set_map_type)."""
 
     def __init__(self, voxel_size, trunc_dist, W, H, K, win=11, capacity_log2=22, device=0,
-                 zmin=0.5, zmax=3.5, lib=None, _handle=None):
+                 zmin=0.5, zmax=3.5, lib=None, _handle=None, map_type=None):
         self.L = load() if lib is None else lib         # lib: load_test_lib() for the path-forcing tests
         self.h = C.c_void_p()
         self._dev = []                                  # before anything can raise: close() / __del__ walk it
@@ -258,6 +265,8 @@ class GradSdf:
         self.K = _f32(K).reshape(9).copy()
         self._chk(self.L.gsdf_set_zrange(self.h, np.float32(zmin), np.float32(zmax)))
         self._chk(self.L.gsdf_normals_init(self.h, self.W, self.H, _fp(self.K), int(win)))
+        if map_type is not None:
+            self._chk(self.L.gsdf_set_map_type(self.h, int(map_type)))
 
     @classmethod
     def shards(cls, n, voxel_size, trunc_dist, W, H, K, capacity_log2=22, device=0, **kw):
@@ -302,6 +311,16 @@ class GradSdf:
 
     def reset(self):
         self._chk(self.L.gsdf_reset(self.h))
+
+    def set_map_type(self, map_type):
+        """gsdf_set_map_type: MAP_GRAD (MapGradPixelSdf) or MAP_BASE (MapPixelSdf); only while the map is empty"""
+        self._chk(self.L.gsdf_set_map_type(self.h, int(map_type)))
+
+    @property
+    def map_type(self):
+        v = C.c_int(-1)
+        self._chk(self.L.gsdf_get_map_type(self.h, C.byref(v)))
+        return v.value
 
     def set_zrange(self, zmin, zmax):
         """Sdf::set_zmin / set_zmax (Sdf.h:123-129): the depth range of later fusions and tracker passes"""

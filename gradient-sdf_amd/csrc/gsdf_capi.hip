@@ -355,7 +355,9 @@ int enqueue_track(gsdf_ctx* c, const float* depth_dev, int iters, float conv, fl
     tp.n_track_blocks = c->track_blocks;
     tp.sampling = sampling;
     tp.head_done = 0;
-    if (sampling == 1 && c->persist && c->track_rows && c->track_blocks <= 2 * GSDF_TRACK_MAXBLK) {
+    const int base = c->map_type == GSDF_MAP_BASE;
+    /* (k_track_all has the grad gather only: a base context runs the per-pass launches) */
+    if (sampling == 1 && !base && c->persist && c->track_rows && c->track_blocks <= 2 * GSDF_TRACK_MAXBLK) {
         /* the whole optimize() as one launch; the frame's fusion, gated on the device by done && converged, right behind it */
         tp.pass_index = 0;
         tp.rot = 0;
@@ -409,7 +411,7 @@ int enqueue_track(gsdf_ctx* c, const float* depth_dev, int iters, float conv, fl
                 if (hi > lo && (k < 2 || three)) { nj.tile_first = lo; nj.tile_count = hi - lo; job = &nj; }
             }
             prof_scope ps(c, 2);
-            gsdf_launch_track_pass(c->stream, g, depth_dev, c->tab, c->st, c->partials, c->track_blocks, tp, job);
+            gsdf_launch_track_pass(c->stream, g, depth_dev, c->tab, c->st, c->partials, c->track_blocks, tp, job, base);
         }
         /* The fusion is queued behind the FIRST batch unseen (the usual frame ends there and must not wait for the host) and
          * behind the last one (nothing follows it).  Behind the batches in between it would nearly always be a gated launch
@@ -718,6 +720,24 @@ int gsdf_reset(gsdf_ctx* c) {
     c->merged = false;
     c->grow_forget = true;                                   /* auto-grow's block counts describe the old map (a grown table keeps its size) */
     c->occ_dirty = false;                                    /* the table clear zeroed the filters as well */
+    return GSDF_OK;
+}
+
+int gsdf_set_map_type(gsdf_ctx* c, int type) {
+    if (!c) return fail(GSDF_ERR_INVALID, "null context");
+    if (type != GSDF_MAP_GRAD && type != GSDF_MAP_BASE) return fail(GSDF_ERR_INVALID, "unknown map type");
+    if (type == c->map_type) return GSDF_OK;
+    int64_t n = 0;
+    const int rc = gsdf_count(c, &n);
+    if (rc) return rc;
+    if (n != 0) return fail(GSDF_ERR_INVALID, "the map type can only change while the map is empty (gsdf_reset first)");
+    c->map_type = type;
+    return GSDF_OK;
+}
+
+int gsdf_get_map_type(gsdf_ctx* c, int* type) {
+    if (!c || !type) return fail(GSDF_ERR_INVALID, "null argument");
+    *type = c->map_type;
     return GSDF_OK;
 }
 
@@ -1232,6 +1252,7 @@ int gsdf_ba_setup(gsdf_ctx* c, int n, const float* images_bgr_host, const float*
     GSDF_FLUSH(c);
     int rc = require_frame(c);
     if (rc) return rc;
+    if (c->map_type != GSDF_MAP_GRAD) return fail(GSDF_ERR_INVALID, "PhotoBA needs the Gradient-SDF map (a base-sdf context has no gradient)");
     if (!c->vis) return fail(GSDF_ERR_INVALID, "PhotoBA needs the vis_ bit-vectors: call gsdf_enable_vis before fusing");
     if (n <= 0 || n > 64 || !images_bgr_host || !poses16_host || !frame_idx) return fail(GSDF_ERR_INVALID, "bad argument (1..64 keyframes)");
     HIP_TRY(hipSetDevice(c->device));
@@ -1459,7 +1480,8 @@ int gsdf_query(gsdf_ctx* c, const float* pts_host, int64_t n, float* dist, float
     float *dp = d, *dd = d + 3 * n, *dg = d + 4 * n, *dw = d + 7 * n;
     hipError_t e = hipMemcpyAsync(dp, pts_host, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-        gsdf_launch_query(c->stream, c->tab, c->voxel_size, c->voxel_size_inv, dp, n, dd, dg, dw);
+        gsdf_launch_query(c->stream, c->tab, c->voxel_size, c->voxel_size_inv, dp, n, dd, dg, dw,
+                          c->map_type == GSDF_MAP_BASE ? c->T : -1.f);
         e = hipMemcpyAsync(dist, dd, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
     }
     if (e == hipSuccess) e = hipMemcpyAsync(grad, dg, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);

@@ -48,6 +48,7 @@ struct gsdf_ctx {
     /* MapGradPixelSdf / Sdf members */
     float voxel_size = 0, voxel_size_inv = 0, T = 0, inv_T = 0;
     float zmin = 0.5f, zmax = 3.5f;                /* Sdf.h:67-68 */
+    int map_type = GSDF_MAP_GRAD;                  /* gsdf_set_map_type: GSDF_MAP_BASE = MapPixelSdf (gather and query differ) */
     int factor = 0;
     /* table */
     int capacity_log2 = 0;

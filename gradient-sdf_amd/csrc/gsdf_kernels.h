@@ -160,7 +160,8 @@ int  gsdf_normals_tiles(int W, int H);       /* normals tiles of a frame (workgr
 void gsdf_launch_track_none(hipStream_t s, gsdf_dev_state* st);
 void gsdf_launch_track_pass(hipStream_t s, const gsdf_frame_geom& g, const float* depth, gsdf_table tab,
                             gsdf_dev_state* st, double* partials /* 3 * GSDF_TRACK_ROWSET, zeroed */, int n_blocks,
-                            const gsdf_track_params& tp, const gsdf_normals_job* normals /* nullable */);
+                            const gsdf_track_params& tp, const gsdf_normals_job* normals /* nullable */,
+                            int base = 0 /* 1: MapPixelSdf gather (k_track_pass_base) */);
 /* optimize() as ONE launch (k_track_all): n_blocks co-resident workgroups exchange their sums through `rows`
  * (gsdf_track_all_rows_bytes(n_blocks), zeroed once); n_blocks <= 2 * GSDF_TRACK_MAXBLK */
 void gsdf_launch_track_all(hipStream_t s, const gsdf_frame_geom& g, const float* depth, gsdf_table tab, gsdf_dev_state* st,
@@ -177,7 +178,7 @@ void gsdf_launch_export_raw(hipStream_t s, gsdf_table tab, size_t n_slots, int32
 void gsdf_launch_merge_raw(hipStream_t s, gsdf_table tab, const int32_t* keys, const float* payload,
                            long long n, gsdf_dev_state* st);
 void gsdf_launch_query(hipStream_t s, gsdf_table tab, float vs, float inv_vs, const float* pts, long long n,
-                       float* dist, float* grad, float* w);
+                       float* dist, float* grad, float* w, float base_T = -1.f /* >= 0: MapPixelSdf query with truncation T */);
 void gsdf_launch_get_voxels(hipStream_t s, gsdf_table tab, const int32_t* keys, long long n, float* payload, int32_t* found);
 
 void gsdf_launch_raycast(hipStream_t s, gsdf_table tab, float vs, float inv_vs, int factor /* band half-width in voxels */, int W, int H, const float K[9],

@@ -7,6 +7,7 @@
  *   k_track_pass     RigidPointOptimizer::optimize_sampled, one Gauss-Newton pass
  *                                                      sdf_tracker/RigidPointOptimizer.cpp:51-96
  *   k_query          MapGradPixelSdf::weights / tsdf   sdf_tracker/MapGradPixelSdf.h:109-125
+ *   k_track_pass<., true>, k_query_base   the same for MapPixelSdf (interp3)   sdf_tracker/MapPixelSdf.cpp:43-111
  *
  * Compile with -ffp-contract=off: voxel keys must be bit-identical to the CPU oracle.
  * There is no dense contraction anywhere on this path, hence no MFMA; the kernels are
@@ -1939,14 +1940,155 @@ __device__ __forceinline__ void trk_gather(const gsdf_frame_geom& g, const gsdf_
     }
 }
 
+/* ------------------------------------------------------------------------------------------------
+ * MapPixelSdf (the plain-SDF baseline, --scan-type base-sdf): weights() and tsdf() = interp3() at one point.
+ *
+ * The map is the one k_fuse builds (MapPixelSdf::update visits the same voxels with the same weight / truncate / running mean
+ * as MapGradPixelSdf::update, MapPixelSdfOmp.cpp:163-186); only the query differs: trilinear interpolation of the 8 voxels
+ * around floor(p / vs) instead of the first-order expansion at round(p / vs).
+ * The 2x2x2 cube touches 1, 2, 4 or 8 blocks of 4x4x4 (one per axis unless that axis' floor index is 3 mod 4); only the
+ * distinct ones are looked up, together (gsdf_block_lookup_n: their probe chains overlap).  Block entry e (bit 0 x, 1 y, 2 z)
+ * holds corner c's block when e == (c & span).  A corner exists iff its block exists and its record has w > 0 (the rule of
+ * k_export); its dist is s / w, computed as k_export computes it.
+ * ---------------------------------------------------------------------------------------------- */
+struct base_sample {
+    float w;                 /* weights(): weight of the round(p / vs) voxel if all 8 corners exist, else 0 */
+    float phi;               /* tsdf(): -T if no corner exists, 0 if some do, the interpolation if all do */
+    gsdf_v3 grad;            /* its gradient (0 unless all 8 exist) */
+};
+__device__ __forceinline__ base_sample gsdf_base_sample(const gsdf_table& tab, float inv_vs, float T, gsdf_v3 p) {
+    /* MapPixelSdf.cpp:44-55 */
+    const float pi = inv_vs * p.x, pj = inv_vs * p.y, pk = inv_vs * p.z;
+    const int im = (int)floorf(pi), jm = (int)floorf(pj), km = (int)floorf(pk);
+    const float dx = pi - (float)im, dy = pj - (float)jm, dz = pk - (float)km;
+    /* corners outside the key range do not exist; a block of such a corner holds no in-range corner (2^20 is a multiple of 4) */
+    const uint32_t inx = (gsdf_key_in_range(im, 0, 0) ? 1u : 0u) | (gsdf_key_in_range(im + 1, 0, 0) ? 2u : 0u);
+    const uint32_t iny = (gsdf_key_in_range(0, jm, 0) ? 1u : 0u) | (gsdf_key_in_range(0, jm + 1, 0) ? 2u : 0u);
+    const uint32_t inz = (gsdf_key_in_range(0, 0, km) ? 1u : 0u) | (gsdf_key_in_range(0, 0, km + 1) ? 2u : 0u);
+    const uint32_t span = ((im & 3) == 3 ? 1u : 0u) | ((jm & 3) == 3 ? 2u : 0u) | ((km & 3) == 3 ? 4u : 0u);
+    unsigned long long bk[8], k[8];
+    uint32_t h[8];
+    int blk[8];
+    uint32_t pend = 0u;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int i0 = e & 1, j0 = (e >> 1) & 1, k0 = (e >> 2) & 1;
+        const bool want = (e & ~span) == 0u && ((inx >> i0) & 1u) && ((iny >> j0) & 1u) && ((inz >> k0) & 1u);
+        bk[e] = want ? gsdf_block_key(gsdf_key_pack(im + i0, jm + j0, km + k0)) : 0ull;
+        h[e] = gsdf_hash(bk[e]) & tab.block_mask;
+        k[e] = want ? tab.bkeys[h[e]] : GSDF_KEY_EMPTY;
+        pend |= want ? 1u << e : 0u;
+    }
+    gsdf_block_lookup_n<8, false>(tab, bk, h, k, pend, blk);
+    /* the 8 corners, d[i0 + 2 j0 + 4 k0] (MapPixelSdf.cpp:58-69) */
+    float d[8], wv[8];
+    uint32_t present = 0u;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        int b = blk[0];                                                   /* blk[c & span] as a select chain (span is not a constant) */
+#pragma unroll
+        for (int e = 1; e < 8; ++e)
+            if ((e & ~c) == 0) b = (uint32_t)e == (c & span) ? blk[e] : b;
+        const int i0 = c & 1, j0 = (c >> 1) & 1, k0 = (c >> 2) & 1;
+        float2 ws = make_float2(0.f, 0.f);
+        if (b >= 0 && ((inx >> i0) & (iny >> j0) & (inz >> k0) & 1u)) {
+            const unsigned long long key = gsdf_key_pack(im + i0, jm + j0, km + k0);
+            ws = *reinterpret_cast<const float2*>(tab.vox + ((size_t)b * GSDF_BLOCK_VOX + gsdf_block_local(key)));
+        }
+        const bool ex = ws.x > 0.f;
+        present |= ex ? 1u << c : 0u;
+        wv[c] = ws.x;
+        d[c] = ex ? ws.y / ws.x : 0.f;
+    }
+    base_sample r;
+    r.w = 0.f;
+    r.grad = gsdf_v3{ 0.f, 0.f, 0.f };
+    if (present == 0u) { r.phi = -T; return r; }                           /* :71-72, extrap = -T_ (MapPixelSdf.h:111) */
+    if (present != 0xFFu) { r.phi = 0.f; return r; }                       /* :106 */
+    /* weights(): the round(p / vs) voxel (MapPixelSdf.h:136-139, float2vox = std::round of the same product) is one of the corners */
+    {
+        const int c = (gsdf_roundf(pi) != (float)im ? 1 : 0) | (gsdf_roundf(pj) != (float)jm ? 2 : 0) | (gsdf_roundf(pk) != (float)km ? 4 : 0);
+        float wr = 0.f;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) wr = q == c ? wv[q] : wr;             /* (a select chain: no indexed register array) */
+        r.w = wr;
+    }
+    /* interp3, all 8 corners (MapPixelSdf.cpp:74-103), in its operation order */
+    const float d01 = (1.f - dx) * d[0] + dx * d[1];
+    const float d23 = (1.f - dx) * d[2] + dx * d[3];
+    const float d45 = (1.f - dx) * d[4] + dx * d[5];
+    const float d67 = (1.f - dx) * d[6] + dx * d[7];
+    const float d02 = (1.f - dy) * d[0] + dy * d[2];
+    const float d13 = (1.f - dy) * d[1] + dy * d[3];
+    const float d46 = (1.f - dy) * d[4] + dy * d[6];
+    const float d57 = (1.f - dy) * d[5] + dy * d[7];
+    r.grad.x = inv_vs * ((1.f - dz) * d13 + dz * d57 - (1.f - dz) * d02 - dz * d46);
+    r.grad.y = inv_vs * ((1.f - dz) * d23 + dz * d67 - (1.f - dz) * d01 - dz * d45);
+    r.grad.z = inv_vs * ((1.f - dy) * d45 + dy * d67 - (1.f - dy) * d01 - dy * d23);
+    const float dy0 = (1.f - dy) * d01 + dy * d23;
+    const float dy1 = (1.f - dy) * d45 + dy * d67;
+    r.phi = (1.f - dz) * dy0 + dz * dy1;
+    return r;
+}
+
+/* trk_gather for a MapPixelSdf map (RigidPointOptimizer.cpp:62-81 with weights() / tsdf() of MapPixelSdf).  The same lanes take
+ * the same pixels as in trk_gather (x-adjacent pixels in adjacent lanes: their cubes share record lines), one pixel at a time:
+ * a pixel's 8-block lookup and 8 record loads are its independent loads in flight. */
+template <int PPT>
+__device__ __forceinline__ void trk_gather_base(const gsdf_frame_geom& g, const gsdf_table& tab, const float* __restrict__ depth,
+                                                const float pose[7], int pix0, int pix_stride, int batch_stride,
+                                                float (&acc)[GSDF_TRACK_NSUM], const int xy_scale = 1) {
+    float R[9];
+    gsdf_quat_to_R(pose + 3, R);                                          /* RigidPointOptimizer.cpp:53-54 */
+    const float t[3] = { pose[0], pose[1], pose[2] };
+    const float fx_inv = 1.f / g.fx, fy_inv = 1.f / g.fy;                 /* :46-47 */
+    const int N = g.W * g.H;
+    const uint32_t uW = (uint32_t)g.W;
+#pragma unroll 1
+    for (int base = pix0; base < N; base += batch_stride) {
+#pragma unroll 1
+        for (int j = 0; j < PPT; ++j) {
+            const int pix = base + j * pix_stride;
+            if (pix >= N) break;
+            const float z = depth[pix];
+            if (z <= g.zmin || z >= g.zmax) continue;                     /* :64-65 */
+            const uint32_t py = (uint32_t)pix / uW, px = (uint32_t)pix - py * uW;
+            const int y = (int)py * xy_scale, x = (int)px * xy_scale;
+            const float x0 = ((float)x - g.cx) * fx_inv;                  /* :67-68 */
+            const float y0 = ((float)y - g.cy) * fy_inv;
+            const gsdf_v3 pc = { x0 * z, y0 * z, z };
+            const gsdf_v3 Rp = gsdf_matvec(R, pc);
+            const gsdf_v3 p = { Rp.x + t[0], Rp.y + t[1], Rp.z + t[2] };  /* :70 */
+            const base_sample bs = gsdf_base_sample(tab, g.inv_vs, g.T, p);
+            if (!(bs.w > 0.f)) continue;                                  /* :72-73 */
+            const float phi = bs.phi;
+            const gsdf_v3 gr = bs.grad;
+            const gsdf_v3 pxg = gsdf_cross3(p, gr);                       /* :78 */
+            const float J[6] = { gr.x, gr.y, gr.z, pxg.x, pxg.y, pxg.z };
+            acc[0] += phi * phi;                                          /* :76 */
+#pragma unroll
+            for (int i = 0; i < 6; ++i) acc[1 + i] += phi * J[i];         /* :79 */
+            int q = 7;
+#pragma unroll
+            for (int i = 0; i < 6; ++i)
+#pragma unroll
+                for (int jj = i; jj < 6; ++jj) acc[q++] += J[i] * J[jj];  /* :80 */
+            acc[28] += 1.f;                                               /* :81 */
+        }
+    }
+}
+
 static_assert(GSDF_TRACK_BLOCK == NRM_THREADS, "the normals tiles of the first pass run in tracker-sized workgroups");
 /* SAMPLED: optimize_sampled(depth, K, sampling > 1) -- the public stride argument of RigidPointOptimizer.h:65.  g.W x g.H is
  * the grid of sampled pixels (ceil(W / s) x ceil(H / s)), `depth` its compacted image (k_subsample), tp.sampling the stride.
  * A second instantiation so that the sampling-1 kernel of the frame loop stays instruction for instruction what it was. */
-template <bool SAMPLED>
-__global__ __launch_bounds__(GSDF_TRACK_BLOCK, 4) void k_track_pass(gsdf_frame_geom g, const float* __restrict__ depth,
-                                                                 gsdf_table tab, gsdf_dev_state* st,
-                                                                 double* rows, gsdf_track_params tp, gsdf_normals_job nj) {
+/* BASE: the pass over a MapPixelSdf map (trk_gather_base); the rest of the kernel is the same for both map types.  Its
+ * instantiations run at 2 waves per SIMD (up to 256 VGPRs; they use 173, no scratch): a pixel's 8-block lookup does not fit the
+ * grad pass' 128. */
+template <bool SAMPLED, bool BASE>
+__global__ __launch_bounds__(GSDF_TRACK_BLOCK, BASE ? 2 : 4) void k_track_pass(gsdf_frame_geom g, const float* __restrict__ depth,
+                                                                            gsdf_table tab, gsdf_dev_state* st,
+                                                                            double* rows, gsdf_track_params tp, gsdf_normals_job nj) {
     /* Workgroups beyond the tracker's own (first pass of a frame in the Scan3D loop only): one normals tile each
      * (NormalEstimator::compute of THIS depth frame for the update() that follows a converged optimize(),
      * main_scan_3d.cpp:258-263).  They need the depth only, fill the chip beside the latency-bound pass, and use
@@ -2047,8 +2189,13 @@ __global__ __launch_bounds__(GSDF_TRACK_BLOCK, 4) void k_track_pass(gsdf_frame_g
 #pragma unroll
             for (int i = 0; i < GSDF_TRACK_NSUM; ++i) dummy[i] = 0.f;
             const int xy_scale_w = SAMPLED ? tp.sampling : 1;
-            if (trk_heavy) trk_gather<TRK_PPT>(g, tab, depth, z_pre, pose_old, trk_pix0, 64, trk_batch, dummy, nullptr, xy_scale_w);
-            else trk_gather<TRK_PPT - 1>(g, tab, depth, z_pre, pose_old, trk_pix0, 64, trk_batch, dummy, nullptr, xy_scale_w);
+            if constexpr (BASE) {
+                if (trk_heavy) trk_gather_base<TRK_PPT>(g, tab, depth, pose_old, trk_pix0, 64, trk_batch, dummy, xy_scale_w);
+                else trk_gather_base<TRK_PPT - 1>(g, tab, depth, pose_old, trk_pix0, 64, trk_batch, dummy, xy_scale_w);
+            } else {
+                if (trk_heavy) trk_gather<TRK_PPT>(g, tab, depth, z_pre, pose_old, trk_pix0, 64, trk_batch, dummy, nullptr, xy_scale_w);
+                else trk_gather<TRK_PPT - 1>(g, tab, depth, z_pre, pose_old, trk_pix0, 64, trk_batch, dummy, nullptr, xy_scale_w);
+            }
             if (dummy[28] == -1.f) st->dbg[20] = 1ull;                    /* (never: a count; keeps the loads alive) */
         }
         if (wave == 0) {
@@ -2114,8 +2261,13 @@ __global__ __launch_bounds__(GSDF_TRACK_BLOCK, 4) void k_track_pass(gsdf_frame_g
 #pragma unroll
     for (int i = 0; i < GSDF_TRACK_NSUM; ++i) acc[i] = 0.f;
     const int xy_scale = SAMPLED ? tp.sampling : 1;
-    if (trk_heavy) trk_gather<TRK_PPT>(g, tab, depth, z_pre, pose, trk_pix0, 64, trk_batch, acc, trk_tr ? trk_tr + 8 + wave : nullptr, xy_scale);
-    else trk_gather<TRK_PPT - 1>(g, tab, depth, z_pre, pose, trk_pix0, 64, trk_batch, acc, trk_tr ? trk_tr + 8 + wave : nullptr, xy_scale);
+    if constexpr (BASE) {
+        if (trk_heavy) trk_gather_base<TRK_PPT>(g, tab, depth, pose, trk_pix0, 64, trk_batch, acc, xy_scale);
+        else trk_gather_base<TRK_PPT - 1>(g, tab, depth, pose, trk_pix0, 64, trk_batch, acc, xy_scale);
+    } else {
+        if (trk_heavy) trk_gather<TRK_PPT>(g, tab, depth, z_pre, pose, trk_pix0, 64, trk_batch, acc, trk_tr ? trk_tr + 8 + wave : nullptr, xy_scale);
+        else trk_gather<TRK_PPT - 1>(g, tab, depth, z_pre, pose, trk_pix0, 64, trk_batch, acc, trk_tr ? trk_tr + 8 + wave : nullptr, xy_scale);
+    }
     if (trk_tr && threadIdx.x == 0) trk_tr[2] = wall_clock64();                         /* wave 0: gather done */
     /* every wave reduces its sums as soon as its own gather is done (wsum is used here only): ONE barrier per pass tail */
     wave_sum_to_lane63(acc);
@@ -2142,7 +2294,7 @@ __global__ __launch_bounds__(GSDF_TRACK_BLOCK, 4) void k_track_pass(gsdf_frame_g
 int gsdf_normals_tiles(int W, int H) { return ((W + NRM_TX - 1) / NRM_TX) * ((H + NRM_TY - 1) / NRM_TY); }
 void gsdf_launch_track_pass(hipStream_t s, const gsdf_frame_geom& g, const float* depth, gsdf_table tab,
                             gsdf_dev_state* st, double* partials, int n_blocks, const gsdf_track_params& tp_in,
-                            const gsdf_normals_job* normals) {
+                            const gsdf_normals_job* normals, int base) {
     gsdf_track_params tp = tp_in;
     /* one chunk of TRK_CHUNK pixels per workgroup while the grid allows it (640 x 480: 240 workgroups), more by looping */
     {                                   /* ... and then the same number of chunks for every workgroup (1280 x 960: 480 x 2, not 512 x 1.9) */
@@ -2165,10 +2317,15 @@ void gsdf_launch_track_pass(hipStream_t s, const gsdf_frame_geom& g, const float
         extra = std::max(0, nj.tile_count > 0 ? std::min(nj.tile_count, rest) : rest);
         dyn = extra ? sizeof(nrm_lds) : 0;
     }
-    if (tp.sampling > 1)
-        hipLaunchKernelGGL(k_track_pass<true>, dim3(n_blocks + extra), dim3(GSDF_TRACK_BLOCK), dyn, s, g, depth, tab, st, partials, tp, nj);
+    if (base) {
+        if (tp.sampling > 1)
+            hipLaunchKernelGGL((k_track_pass<true, true>), dim3(n_blocks + extra), dim3(GSDF_TRACK_BLOCK), dyn, s, g, depth, tab, st, partials, tp, nj);
+        else
+            hipLaunchKernelGGL((k_track_pass<false, true>), dim3(n_blocks + extra), dim3(GSDF_TRACK_BLOCK), dyn, s, g, depth, tab, st, partials, tp, nj);
+    } else if (tp.sampling > 1)
+        hipLaunchKernelGGL((k_track_pass<true, false>), dim3(n_blocks + extra), dim3(GSDF_TRACK_BLOCK), dyn, s, g, depth, tab, st, partials, tp, nj);
     else
-        hipLaunchKernelGGL(k_track_pass<false>, dim3(n_blocks + extra), dim3(GSDF_TRACK_BLOCK), dyn, s, g, depth, tab, st, partials, tp, nj);
+        hipLaunchKernelGGL((k_track_pass<false, false>), dim3(n_blocks + extra), dim3(GSDF_TRACK_BLOCK), dyn, s, g, depth, tab, st, partials, tp, nj);
 }
 
 /* the sampled pixels of optimize_sampled (RigidPointOptimizer.cpp:62: y = 0, s, 2s, ... < H; x likewise), compacted row-major */
@@ -2517,11 +2674,26 @@ __global__ __launch_bounds__(256) void k_query(gsdf_table tab, float vs, float i
         grad[3 * i] = og.x; grad[3 * i + 1] = og.y; grad[3 * i + 2] = og.z;
     }
 }
+/* MapPixelSdf::weights + ::tsdf at arbitrary points -- MapPixelSdf.h:108-143, MapPixelSdf.cpp:43-111 */
+__global__ __launch_bounds__(256) void k_query_base(gsdf_table tab, float inv_vs, float T, const float* pts, long long n,
+                                                    float* dist, float* grad, float* w) {
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (; i < n; i += stride) {
+        const gsdf_v3 p = { pts[3 * i], pts[3 * i + 1], pts[3 * i + 2] };
+        const base_sample r = gsdf_base_sample(tab, inv_vs, T, p);
+        w[i] = r.w; dist[i] = r.phi;
+        grad[3 * i] = r.grad.x; grad[3 * i + 1] = r.grad.y; grad[3 * i + 2] = r.grad.z;
+    }
+}
 void gsdf_launch_query(hipStream_t s, gsdf_table tab, float vs, float inv_vs, const float* pts, long long n,
-                       float* dist, float* grad, float* w) {
+                       float* dist, float* grad, float* w, float base_T) {
     if (n <= 0) return;
     const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    hipLaunchKernelGGL(k_query, dim3(blocks), dim3(256), 0, s, tab, vs, inv_vs, pts, n, dist, grad, w);
+    if (base_T >= 0.f)
+        hipLaunchKernelGGL(k_query_base, dim3(blocks), dim3(256), 0, s, tab, inv_vs, base_T, pts, n, dist, grad, w);
+    else
+        hipLaunchKernelGGL(k_query, dim3(blocks), dim3(256), 0, s, tab, vs, inv_vs, pts, n, dist, grad, w);
 }
 
 /* tsdf_.at(idx) for n voxel indices -- MapGradPixelSdf.h:127-129 (getSdf): the stored SdfVoxel (dist, raw gradient sum, weight) */

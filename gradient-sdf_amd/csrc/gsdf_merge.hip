@@ -577,6 +577,7 @@ int gsdf_merge_from(gsdf_ctx* dst, gsdf_ctx* src) {
     if (!dst || !src || dst == src) return gsdf_fail(GSDF_ERR_INVALID, "gsdf_merge_from: two different contexts are needed");
     if (dst->device != src->device) return gsdf_fail(GSDF_ERR_INVALID, "gsdf_merge_from: the contexts live on different devices (use gsdf_merge_allreduce between devices)");
     if (dst->voxel_size != src->voxel_size || dst->T != src->T) return gsdf_fail(GSDF_ERR_INVALID, "gsdf_merge_from: voxel size / truncation differ");
+    if (dst->map_type != src->map_type) return gsdf_fail(GSDF_ERR_INVALID, "gsdf_merge_from: the contexts have different map types");
     if ((dst->vis != nullptr) != (src->vis != nullptr) || (dst->vis && dst->vis_words != src->vis_words))
         return gsdf_fail(GSDF_ERR_INVALID, "gsdf_merge_from: gsdf_enable_vis must have been called alike on both contexts");
     HIP_TRY(hipSetDevice(dst->device));

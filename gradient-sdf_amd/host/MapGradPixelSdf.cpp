@@ -20,7 +20,23 @@ MapGradPixelSdf::MapGradPixelSdf(float voxel_size, float T, int capacity_log2, i
     if (max_capacity_log2 > capacity_log2) check(gsdf_set_auto_grow(ctx_, max_capacity_log2), "gsdf_set_auto_grow");
 }
 
+MapGradPixelSdf::MapGradPixelSdf(int map_type, float voxel_size, float T, int capacity_log2, int device, int max_capacity_log2)
+    : voxel_size_(voxel_size), T_(T) {
+    check(gsdf_create(&ctx_, voxel_size, T, capacity_log2, device), "gsdf_create");
+    /* (the destructor does not run when a constructor throws) */
+    if (gsdf_set_map_type(ctx_, map_type) != GSDF_OK) {
+        const std::string e = gsdf_last_error();
+        gsdf_destroy(ctx_);
+        throw std::runtime_error("gsdf_set_map_type: " + e);
+    }
+    if (max_capacity_log2 > capacity_log2) check(gsdf_set_auto_grow(ctx_, max_capacity_log2), "gsdf_set_auto_grow");
+}
+
 MapGradPixelSdf::~MapGradPixelSdf() { gsdf_destroy(ctx_); }
+
+void MapGradPixelSdf::query1(const Vec3f& point, float* d, float* g, float* w) const {
+    check(gsdf_query(ctx_, point.data(), 1, d, g, w), "gsdf_query");
+}
 
 void MapGradPixelSdf::ensure_frame(const DepthImage& depth, const Mat3f& K, NormalEstimator* NEst) {
     if (frame_w_ == depth.cols && frame_h_ == depth.rows) return;

@@ -63,6 +63,11 @@ public:
     gsdf_ctx* handle() const { return ctx_; }
     float voxel_size() const { return voxel_size_; }
 
+protected:
+    /* a context of another map type (gsdf_set_map_type): MapPixelSdf */
+    MapGradPixelSdf(int map_type, float voxel_size, float T, int capacity_log2, int device, int max_capacity_log2);
+    void query1(const Vec3f& point, float* d, float* g, float* w) const;
+
 private:
     float zmin_ = 0.5f, zmax_ = 3.5f;                                  /* Sdf.h:67-68 */
 };

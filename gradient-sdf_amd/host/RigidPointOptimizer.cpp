@@ -8,7 +8,7 @@
 
 bool RigidPointOptimizer::optimize_sampled(const DepthImage& depth, const Mat3f K, size_t sampling) {
     MapGradPixelSdf* map = dynamic_cast<MapGradPixelSdf*>(tSDF_);
-    if (!map) throw std::runtime_error("RigidPointOptimizer needs a MapGradPixelSdf");
+    if (!map) throw std::runtime_error("RigidPointOptimizer needs a MapGradPixelSdf or a MapPixelSdf");
     int conv = 0, passes = 0;
     const int rc = gsdf_track_sampled(map->ctx_, depth.data(), K.data(), pose_.pose7(), num_iterations_, conv_threshold_,
                                       damping_, (int)std::min<size_t>(sampling, 1u << 20), &conv, &passes);

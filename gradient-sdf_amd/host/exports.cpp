@@ -54,8 +54,28 @@ bool write_cloud_ply(gsdf_ctx* ctx, float voxel_size, const std::string& filenam
     return true;
 }
 
-/* save_sdf -- MapGradPixelSdf.cpp:222-296: sparse "lin_idx value" text files + grid info. */
-bool write_sdf_txt(gsdf_ctx* ctx, float voxel_size, const std::string& filename) {
+bool write_points_ply(gsdf_ctx* ctx, float voxel_size, const std::string& filename, long* n_rows) {
+    std::vector<int32_t> k;
+    std::vector<float> p;
+    if (!export_arrays(ctx, k, p)) return false;
+    std::vector<std::array<float, 3>> pts;
+    for (size_t i = 0; i < k.size() / 3; ++i) {
+        if (p[5 * i + 4] < 5) continue;                                  /* MapPixelSdf.cpp:246-247 */
+        if (std::fabs(p[5 * i]) < std::sqrt(3) * voxel_size)             /* :248 (double) */
+            pts.push_back({ voxel_size * (float)k[3 * i], voxel_size * (float)k[3 * i + 1], voxel_size * (float)k[3 * i + 2] });
+    }
+    if (n_rows) *n_rows = (long)pts.size();
+    std::ofstream f(filename.c_str());
+    if (!f.is_open()) return false;
+    f << "ply\nformat ascii 1.0\nelement vertex " << pts.size() << "\n"
+      << "property float x\nproperty float y\nproperty float z\nend_header\n";
+    for (const auto& q : pts) f << q[0] << " " << q[1] << " " << q[2] << "\n";
+    return true;
+}
+
+/* save_sdf -- MapGradPixelSdf.cpp:222-296: sparse "lin_idx value" text files + grid info (MapPixelSdf.cpp:285-347: the same
+ * without the gradient files) */
+bool write_sdf_txt(gsdf_ctx* ctx, float voxel_size, const std::string& filename, bool normals) {
     std::vector<int32_t> k;
     std::vector<float> p;
     if (!export_arrays(ctx, k, p)) return false;
@@ -71,8 +91,11 @@ bool write_sdf_txt(gsdf_ctx* ctx, float voxel_size, const std::string& filename)
          << "voxel min: " << mn[0] << " " << mn[1] << " " << mn[2] << "\n"
          << "voxel max: " << mx[0] << " " << mx[1] << " " << mx[2] << "\n";
     std::ofstream fd((filename + "_sdf_d.txt").c_str()), fw((filename + "_sdf_weight.txt").c_str());
-    std::ofstream f0((filename + "_sdf_n0.txt").c_str()), f1((filename + "_sdf_n1.txt").c_str()), f2((filename + "_sdf_n2.txt").c_str());
-    if (!fd.is_open() || !fw.is_open() || !f0.is_open() || !f1.is_open() || !f2.is_open()) {
+    std::ofstream f0, f1, f2;
+    if (normals) {
+        f0.open((filename + "_sdf_n0.txt").c_str()); f1.open((filename + "_sdf_n1.txt").c_str()); f2.open((filename + "_sdf_n2.txt").c_str());
+    }
+    if (!fd.is_open() || !fw.is_open() || (normals && (!f0.is_open() || !f1.is_open() || !f2.is_open()))) {
         std::cerr << "couldn't save sdf or sdf weight file!" << std::endl;
         return false;
     }
@@ -80,6 +103,7 @@ bool write_sdf_txt(gsdf_ctx* ctx, float voxel_size, const std::string& filename)
         const int lin = dim[0] * dim[1] * (k[3 * i + 2] - mn[2]) + dim[0] * (k[3 * i + 1] - mn[1]) + k[3 * i] - mn[0];
         fd << lin << " " << p[5 * i] << "\n";
         fw << lin << " " << p[5 * i + 4] << "\n";
+        if (!normals) continue;
         f0 << lin << " " << p[5 * i + 1] << "\n";
         f1 << lin << " " << p[5 * i + 2] << "\n";
         f2 << lin << " " << p[5 * i + 3] << "\n";

@@ -12,8 +12,10 @@
 namespace gsdf_exports {
 /* extract_pc -- MapGradPixelSdf.cpp:177-220; *n_rows (nullable) = points written */
 bool write_cloud_ply(gsdf_ctx* ctx, float voxel_size, const std::string& filename, long* n_rows);
-/* save_sdf -- MapGradPixelSdf.cpp:222-296 */
-bool write_sdf_txt(gsdf_ctx* ctx, float voxel_size, const std::string& filename);
+/* extract_pc -- MapPixelSdf.cpp:242-277: voxel centres only (weight >= 5, |dist| < sqrt(3) vs) */
+bool write_points_ply(gsdf_ctx* ctx, float voxel_size, const std::string& filename, long* n_rows);
+/* save_sdf -- MapGradPixelSdf.cpp:222-296; normals = false: MapPixelSdf.cpp:285-347 (no _sdf_n* files) */
+bool write_sdf_txt(gsdf_ctx* ctx, float voxel_size, const std::string& filename, bool normals = true);
 /* extract_mesh -- MapGradPixelSdf.cpp:124-175, marching cubes on the device; *n_faces (nullable) = faces written */
 bool write_mesh_ply(gsdf_ctx* ctx, float voxel_size, const std::string& filename, long* n_faces);
 }

@@ -17,7 +17,8 @@
  *                     the per-voxel sums over the union of blocks), then rank 0 writes the outputs.  Tracked mode does
  *                     not shard (frame i needs the map of all frames < i);
  *   --transport shm   the exchange through host shared memory instead of RCCL: N ranks on ONE device (test boxes).
- * Only --scan-type grad-sdf exists here: base-sdf is the comparison method, out of scope.
+ * --scan-type grad-sdf (MapGradPixelSdf) or base-sdf (MapPixelSdf, the plain-SDF baseline, :99-114 / :226-233); base-sdf runs
+ * on one GPU only (--gpus N > 1 refuses it).
  */
 #include <signal.h>
 #include <sys/wait.h>
@@ -35,6 +36,7 @@
 #include <thread>
 
 #include "MapGradPixelSdf.h"
+#include "MapPixelSdf.h"
 #include "RigidOptimizer.h"
 #include "Timer.h"
 #include "frame_pipeline.h"
@@ -63,7 +65,8 @@ bool parse(int argc, char** argv, Options& o) {
         if (a == "-h" || a == "--help") {
             std::cout << "Hash Table-Based 3D Scanning (MI355X)\n  --input --results --pose-file --first --last --scan-type"
                          " --data-type --voxel-size --trunc --save-sdf --width --height --hash-capacity --hash-max-capacity --device"
-                         " --sync --decode-threads --gpus --transport rccl|shm\n";
+                         " --sync --decode-threads --gpus --transport rccl|shm\n"
+                         "  --scan-type grad-sdf|base-sdf (base-sdf: one GPU only, --gpus 1)\n";
             std::exit(0);
         }
         if (!val(v)) { std::cerr << "missing value for " << a << std::endl; return false; }
@@ -239,10 +242,21 @@ int run(int, char**, Options& opt) {
     const bool lead = !sharded || opt.rank == 0;                                  /* writes the outputs */
     if (sharded && opt.transport != "shm") opt.device = opt.rank;                 /* one GPU per rank */
 
-    if (opt.stype != "grad-sdf") {           /* the default "map-gp" is rejected like in the reference (:105-114) */
+    if (opt.stype != "grad-sdf" && opt.stype != "base-sdf") {   /* the default "map-gp" is rejected like in the reference (:105-114) */
         std::cerr << "Your specified scan type is not supported (yet)." << std::endl;
         return 1;
     }
+    const bool base = opt.stype == "base-sdf";
+    if (base && sharded) {
+        std::cerr << "--scan-type base-sdf runs on one GPU: --gpus must be 1" << std::endl;
+        return 1;
+    }
+    /* :226-233 */
+    auto make_map = [&](float truncation) -> MapGradPixelSdf* {
+        const int max_cap = std::max(opt.capacity_log2, opt.max_capacity_log2);
+        if (base) return new MapPixelSdf(opt.voxel_size, truncation, opt.capacity_log2, opt.device, max_cap);
+        return new MapGradPixelSdf(opt.voxel_size, truncation, opt.capacity_log2, opt.device, max_cap);
+    };
     std::unique_ptr<ImageLoader> loader;
     if (opt.dtype == "tum") loader.reset(new TumrgbdLoader(opt.input));
     else if (opt.dtype == "synth") loader.reset(new SynthLoader(opt.input));
@@ -296,7 +310,7 @@ int run(int, char**, Options& opt) {
             }
             if (i == opt.first) {
                 T.tic();
-                tSDF.reset(new MapGradPixelSdf(opt.voxel_size, truncation, opt.capacity_log2, opt.device, std::max(opt.capacity_log2, opt.max_capacity_log2)));
+                tSDF.reset(make_map(truncation));
                 T.toc("Create Sdf");
                 T.tic();
                 if (GT_pose) tSDF->update(color, depth, K, SE3(poses[0]), &NEst);          /* poses[0] even if --first > 0 (:242) */
@@ -345,7 +359,7 @@ int run(int, char**, Options& opt) {
         Exchange ex;
         if (sharded && !exchange_prepare(ex, opt, opt.device)) return 1;
         T.tic();
-        tSDF.reset(new MapGradPixelSdf(opt.voxel_size, truncation, opt.capacity_log2, opt.device, std::max(opt.capacity_log2, opt.max_capacity_log2)));
+        tSDF.reset(make_map(truncation));
         if (lead) T.toc("Create Sdf");
         tSDF->prepare(opt.width, opt.height, K, &NEst);
         gsdf_ctx* ctx = tSDF->handle();

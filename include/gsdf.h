@@ -91,6 +91,23 @@ int gsdf_grow(gsdf_ctx* c, int new_capacity_log2);
 int gsdf_set_auto_grow(gsdf_ctx* c, int max_capacity_log2);
 int gsdf_capacity(gsdf_ctx* c, int* capacity_log2);
 
+/* Map type -- main_scan_3d.cpp:226-233 (--scan-type): GSDF_MAP_GRAD is MapGradPixelSdf (the default, the Gradient-SDF map),
+ * GSDF_MAP_BASE is MapPixelSdf (sdf_tracker/MapPixelSdf.h:52-157), the plain voxel-hash SDF the paper compares against.  Both
+ * fuse the same voxels with the same weight / truncation / running mean (MapPixelSdfOmp.cpp:163-186 = MapGradPixelSdf.cpp:86-118),
+ * so gsdf_update[_dev], gsdf_export, gsdf_get_voxels, gsdf_raycast*, gsdf_extract_mesh, grow and the next-frame hint are the same
+ * on both.  On a base context the tracker entries (gsdf_track, gsdf_track_sampled, gsdf_track_and_fuse_dev,
+ * gsdf_track_and_fuse_ahead_dev) and gsdf_query use MapPixelSdf::weights / ::tsdf (MapPixelSdf.h:108-143, interp3 at
+ * MapPixelSdf.cpp:43-111): trilinear interpolation of the 8 voxels around floor(p / vs); phi = -T and grad = 0 where none of them
+ * exists, phi = 0 and grad = 0 where some do, and w is the weight of the round(p / vs) voxel only when all 8 exist (else 0).
+ * gsdf_ba_setup (PhotoBA needs the gradient) and gsdf_merge_from between contexts of different type are GSDF_ERR_INVALID on a
+ * base context.  gsdf_merge_raw* and the multi-device merge take raw sums without a type; callers keep them to one type.
+ * gsdf_set_map_type is allowed only while the map is empty (gsdf_count == 0), else GSDF_ERR_INVALID and the type stays as it
+ * was; gsdf_reset keeps the type. */
+#define GSDF_MAP_GRAD 0
+#define GSDF_MAP_BASE 1
+int gsdf_set_map_type(gsdf_ctx* c, int type);
+int gsdf_get_map_type(gsdf_ctx* c, int* type);
+
 /* Sdf::set_zmin / Sdf::set_zmax -- Sdf.h:123-129 (defaults 0.5 / 3.5).  Both bounds finite and zmin < zmax, else
  * GSDF_ERR_INVALID and the range stays as it was.  A change of range withdraws a next-frame hint (gsdf_hint_next_depth_dev):
  * normals computed ahead carry tile statistics taken under the old range. */
