@@ -11,16 +11,22 @@ TUM fr1/xyz-format synthetic stream, 640x480, 1 cm voxels, trunc = 10 voxels, ca
 processes itself (one per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set); under torch.distributed.run it is one of the
 ranks.  Either way a rank asserts WORLD_SIZE == --gpus.
 
-Multi-GPU, two flavours in one run:
+Multi-GPU, two flavours in one run, the second with `--full`:
   * fused+tracked (`value`): tracking makes frame i depend on the map of all frames < i, so the path does not shard --
     N independent replica streams (seed = rank), no data-path collective, `value` = frames of all ranks / max-over-ranks time;
   * `config.sharded` (BASELINE configs[3], the flavour that DOES shard): GT-pose fusion of contiguous frame shards of ONE
     sphere-orbit stream (main_scan_3d.cpp:250-254), `--c4-frames` per rank, then ONE gsdf_merge_allreduce (RCCL all-reduce of
     the per-voxel sums over the union of blocks) on a communicator created outside the timed region, then the mesh on rank 0.
 
+A plain run does only what the headline needs: it renders and uploads the frames, runs the burn-in and timed windows, writes
+--dump-outputs and prints the line.  Everything else measured around it -- the sharded, staged, fused-only and two-stream
+flavours, the default window and configs[2], the roofline replays, the CPU baseline -- runs with `--full` only, and is null
+in the line otherwise (`config.full` says which kind of run printed it).
+
 Output: ONE JSON line on rank 0 (contract in the task statement) including
   value         median of `--repeats` timed windows (each: reset, frame 0, W warm-up steps, barrier, K timed steps, barrier);
                 every run is listed in config.value_runs
+  --full adds:
   roofline      dominant kernel (k_fuse): algorithmic bytes per launch / mean HIP-event duration, measured live in a replay
                 of the same frames; `traffic` (HBM bytes per launch from rocprofv3 PMC passes over THIS command, committed
                 under profiles/ and named in `traffic_source`); `tracker` and `raycast`: the same for k_track_pass / k_raycast
@@ -55,6 +61,10 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5, help="timed windows; value = their median")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the other flavours and configurations, the roofline replays, "
+                         "the CPU baseline (--cpu-frames, --c4-frames, --raycast-reps, --no-staged, --contexts-per-gpu, --no-extras "
+                         "and the two flavour timeouts apply only with it)")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--voxel-size", type=float, default=0.01)
@@ -70,7 +80,8 @@ def parse_args():
     ap.add_argument("--no-extras", action="store_true",
                     help="skip config.default_window (frames 21..220 of the same stream) and config.c3 (BASELINE configs[2])")
     ap.add_argument("--extras-timeout", type=float, default=150.0, help="seconds the two extra configurations may take before the line is printed without them")
-    ap.add_argument("--only-main", action="store_true", help="fused+tracked windows and the roofline replays only (profiling runs)")
+    ap.add_argument("--only-main", action="store_true",
+                    help="with --full: the fused+tracked windows and the roofline replays only (profiling runs)")
     ap.add_argument("--dist-backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for dry runs)")
     ap.add_argument("--single-device", action="store_true",
                     help="dry run of the N>1 code path on a 1-GPU box: every rank uses device 0, the exchange goes through "
@@ -250,7 +261,7 @@ def main():
         return
     global NEXT_HINT
     NEXT_HINT = not args.no_next_hint
-    if args.only_main:
+    if args.only_main or not args.full:         # none of the flavours below (a plain run skips the replays as well)
         args.c4_frames = 0
         args.raycast_reps = 0
         args.cpu_frames = 0
@@ -469,108 +480,111 @@ def main():
         for hp in host:
             g._chk(Lb.gsdf_host_free(g.h, hp))
 
-    # fused-only flavour (GT poses, update only) over the same K frames.  Measured BEFORE the event-timed replay:
-    # recording timing events switches the HIP queue to a slower, profiled dispatch for the rest of the process.
-    # Two rounds, the second one counts: the first long run of back-to-back launches in a process makes the HIP runtime grow
-    # its launch resources once (one launch call of ~40 ms).
-    fused_fps = 0.0
-    for rnd in range(2):
-        g.reset()
-        sync_all()
-        tf = time.perf_counter()
-        for j, i in enumerate(range(1 + Wm, 1 + Wm + K)):
-            g.update_dev(dev[i], frames[i][1], frames[i][2])
-            if j % 32 == 31:
-                g.sync()             # hundreds of launches queued without a sync make the HIP runtime throttle the host
-        t_enq = time.perf_counter() - tf
-        sync_all()
-        fused_fps = K / max_over_ranks([time.perf_counter() - tf])[0]
-    if os.environ.get("GSDF_BENCH_DEBUG"):
-        print("fused-only: enqueue %.1f us/frame, total %.1f us/frame" % (t_enq / K * 1e6, 1e6 / fused_fps), file=sys.stderr)
-
-    # ---- roofline of the dominant kernel: replay the same K frames with HIP events around k_fuse ---
-    # (a separate pass so that event records do not perturb `value`; same frames, same poses)
-    poses = log[:, :7].copy()
-    g.reset()
-    g.update_dev(dev[0], quat_to_R(p0[3:]), t0)
-    for i in range(1, 1 + Wm):
-        if log[i - 1, 7] > 0:
-            g.update_dev(dev[i], quat_to_R(poses[i - 1, 3:]), poses[i - 1, :3])
-    g.sync()
-    st_a = g.stats()
-    g.profile(1)
-    n_fuse = 0
-    for i in range(1 + Wm, 1 + Wm + K):
-        if log[i - 1, 7] > 0:
-            g.update_dev(dev[i], quat_to_R(poses[i - 1, 3:]), poses[i - 1, :3])
-            n_fuse += 1
-    g.sync()
-    prof = g.profile_read()
-    g.profile(0)
-    st_b = g.stats()
-    fuse_ms = prof["fusion"]["ms"] / max(prof["fusion"]["launches"], 1)
-    n_upd_launch = (st_b["n_upd"] - st_a["n_upd"]) / max(n_fuse, 1)
-    alg_bytes = 16.0 * W * H + 52.0 * n_upd_launch            # fusion = 16 N_pix + 52 N_upd
-    achieved = alg_bytes / (fuse_ms * 1e-3) / 1e9 if fuse_ms > 0 else 0.0
-
-    # ---- the tracker's roofline entry: replay the tracked stream with HIP events around every k_track_pass launch ---
-    # one pass moves 4 N_pix (depth) + 32 N_hit (one voxel record per hit) bytes
-    start_stream()
-    g.sync()
-    st_c = g.stats()
-    g.profile(1)
-    for i in range(1 + Wm, 1 + Wm + K):
-        g.track_and_fuse_dev(dev[i])
-    g.sync()
-    prof_t = g.profile_read()
-    trk_each = np.sort(g.profile_launches(2))[::-1]           # every tracker launch by itself, longest first
-    g.profile(0)
-    st_d = g.stats()
-    log_t = g.frame_log()[Wm:Wm + K]
-    trk_passes = float(log_t[:, 8].sum())
-    trk_bytes = 4.0 * W * H * trk_passes + 32.0 * float(st_d["n_hit"] - st_c["n_hit"])
-    trk_ms = prof_t["track_pass"]["ms"]
-    trk_achieved = trk_bytes / (trk_ms * 1e-3) / 1e9 if trk_ms > 0 else 0.0
-    # Per EXECUTED pass: of the launches the host issues (batches of 5, then 8) only `passes` gather; the launch
-    # behind a frame's last pass is head-only (reduce, solve, publish) and those behind the end of optimize() return at once.
-    # The launches that ran a pass are the `passes` longest ones; their median duration is the per-pass figure.
-    n_exec = int(min(trk_passes, len(trk_each)))
-    trk_pass_us = float(np.median(trk_each[:n_exec])) * 1e3 if n_exec else 0.0
-    trk_per_pass = (trk_bytes / max(trk_passes, 1.0)) / (trk_pass_us * 1e-6) / 1e9 if trk_pass_us > 0 else 0.0
-
-    # ---- the raycaster's roofline entry: render the bench map (all 1 + W + K frames tracked and fused) from the last pose ---
-    # bytes per render = 8 per sample the definition evaluates (one block-key probe) + 32 per voxel record read + 16 per pixel
-    # written (depth + normal); samples / records counted on the device (gsdf_raycast_counters)
+    # ---- --full only from here to the CPU baseline: flavours and replays beside the headline, never `value` --------------
+    fused_fps = None
     raycast = None
-    if args.raycast_reps > 0:
-        import ctypes
-        N = W * H
-        buf = ctypes.c_void_p()
-        g._chk(g.L.gsdf_dev_alloc(g.h, ctypes.byref(buf), 4 * N * 4))
-        g._dev.append(buf)
-        nrm = ctypes.c_void_p(buf.value + 4 * N)
-        pose_last = g.get_pose()
-        Rl, tl = quat_to_R(pose_last[3:]), pose_last[:3]
-        g.raycast_dev(Rl, tl, buf, nrm)
+    if args.full:
+        # fused-only flavour (GT poses, update only) over the same K frames.  Measured BEFORE the event-timed replay:
+        # recording timing events switches the HIP queue to a slower, profiled dispatch for the rest of the process.
+        # Two rounds, the second one counts: the first long run of back-to-back launches in a process makes the HIP runtime grow
+        # its launch resources once (one launch call of ~40 ms).
+        fused_fps = 0.0
+        for rnd in range(2):
+            g.reset()
+            sync_all()
+            tf = time.perf_counter()
+            for j, i in enumerate(range(1 + Wm, 1 + Wm + K)):
+                g.update_dev(dev[i], frames[i][1], frames[i][2])
+                if j % 32 == 31:
+                    g.sync()             # hundreds of launches queued without a sync make the HIP runtime throttle the host
+            t_enq = time.perf_counter() - tf
+            sync_all()
+            fused_fps = K / max_over_ranks([time.perf_counter() - tf])[0]
+        if os.environ.get("GSDF_BENCH_DEBUG"):
+            print("fused-only: enqueue %.1f us/frame, total %.1f us/frame" % (t_enq / K * 1e6, 1e6 / fused_fps), file=sys.stderr)
+
+        # ---- roofline of the dominant kernel: replay the same K frames with HIP events around k_fuse ---
+        # (a separate pass so that event records do not perturb `value`; same frames, same poses)
+        poses = log[:, :7].copy()
+        g.reset()
+        g.update_dev(dev[0], quat_to_R(p0[3:]), t0)
+        for i in range(1, 1 + Wm):
+            if log[i - 1, 7] > 0:
+                g.update_dev(dev[i], quat_to_R(poses[i - 1, 3:]), poses[i - 1, :3])
         g.sync()
-        g.raycast_counters(reset=True)
+        st_a = g.stats()
         g.profile(1)
-        for _ in range(args.raycast_reps):
-            g.raycast_dev(Rl, tl, buf, nrm)
+        n_fuse = 0
+        for i in range(1 + Wm, 1 + Wm + K):
+            if log[i - 1, 7] > 0:
+                g.update_dev(dev[i], quat_to_R(poses[i - 1, 3:]), poses[i - 1, :3])
+                n_fuse += 1
         g.sync()
-        pr = g.profile_read_all()["raycast"]
+        prof = g.profile_read()
         g.profile(0)
-        samples, records = g.raycast_counters(reset=True)
-        rc_us = pr["ms"] * 1e3 / max(pr["launches"], 1)
-        rc_bytes = (8.0 * samples + 32.0 * records) / max(args.raycast_reps, 1) + 16.0 * N
-        depth_r = g.download(buf, (H, W), np.float32)
-        hit = depth_r > 0
-        raycast = {"kernel": "k_raycast", "avg_launch_us": round(rc_us, 2), "launches": int(pr["launches"]),
-                   "algorithmic_bytes_per_launch": round(rc_bytes), "achieved": round(rc_bytes / (rc_us * 1e-6) / 1e9, 1) if rc_us > 0 else 0.0,
-                   "frac": round(rc_bytes / (rc_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4) if rc_us > 0 else 0.0,
-                   "samples_per_launch": int(samples // max(args.raycast_reps, 1)), "records_per_launch": int(records // max(args.raycast_reps, 1)),
-                   "hit_fraction": round(float(hit.mean()), 4),
-                   "median_abs_diff_to_input_depth_mm": round(float(np.median(np.abs(depth_r - frames[-1][0])[hit])) * 1e3, 3) if hit.any() else None}
+        st_b = g.stats()
+        fuse_ms = prof["fusion"]["ms"] / max(prof["fusion"]["launches"], 1)
+        n_upd_launch = (st_b["n_upd"] - st_a["n_upd"]) / max(n_fuse, 1)
+        alg_bytes = 16.0 * W * H + 52.0 * n_upd_launch            # fusion = 16 N_pix + 52 N_upd
+        achieved = alg_bytes / (fuse_ms * 1e-3) / 1e9 if fuse_ms > 0 else 0.0
+
+        # ---- the tracker's roofline entry: replay the tracked stream with HIP events around every k_track_pass launch ---
+        # one pass moves 4 N_pix (depth) + 32 N_hit (one voxel record per hit) bytes
+        start_stream()
+        g.sync()
+        st_c = g.stats()
+        g.profile(1)
+        for i in range(1 + Wm, 1 + Wm + K):
+            g.track_and_fuse_dev(dev[i])
+        g.sync()
+        prof_t = g.profile_read()
+        trk_each = np.sort(g.profile_launches(2))[::-1]           # every tracker launch by itself, longest first
+        g.profile(0)
+        st_d = g.stats()
+        log_t = g.frame_log()[Wm:Wm + K]
+        trk_passes = float(log_t[:, 8].sum())
+        trk_bytes = 4.0 * W * H * trk_passes + 32.0 * float(st_d["n_hit"] - st_c["n_hit"])
+        trk_ms = prof_t["track_pass"]["ms"]
+        trk_achieved = trk_bytes / (trk_ms * 1e-3) / 1e9 if trk_ms > 0 else 0.0
+        # Per EXECUTED pass: of the launches the host issues (batches of 5, then 8) only `passes` gather; the launch
+        # behind a frame's last pass is head-only (reduce, solve, publish) and those behind the end of optimize() return at once.
+        # The launches that ran a pass are the `passes` longest ones; their median duration is the per-pass figure.
+        n_exec = int(min(trk_passes, len(trk_each)))
+        trk_pass_us = float(np.median(trk_each[:n_exec])) * 1e3 if n_exec else 0.0
+        trk_per_pass = (trk_bytes / max(trk_passes, 1.0)) / (trk_pass_us * 1e-6) / 1e9 if trk_pass_us > 0 else 0.0
+
+        # ---- the raycaster's roofline entry: render the bench map (all 1 + W + K frames tracked and fused) from the last pose ---
+        # bytes per render = 8 per sample the definition evaluates (one block-key probe) + 32 per voxel record read + 16 per pixel
+        # written (depth + normal); samples / records counted on the device (gsdf_raycast_counters)
+        if args.raycast_reps > 0:
+            import ctypes
+            N = W * H
+            buf = ctypes.c_void_p()
+            g._chk(g.L.gsdf_dev_alloc(g.h, ctypes.byref(buf), 4 * N * 4))
+            g._dev.append(buf)
+            nrm = ctypes.c_void_p(buf.value + 4 * N)
+            pose_last = g.get_pose()
+            Rl, tl = quat_to_R(pose_last[3:]), pose_last[:3]
+            g.raycast_dev(Rl, tl, buf, nrm)
+            g.sync()
+            g.raycast_counters(reset=True)
+            g.profile(1)
+            for _ in range(args.raycast_reps):
+                g.raycast_dev(Rl, tl, buf, nrm)
+            g.sync()
+            pr = g.profile_read_all()["raycast"]
+            g.profile(0)
+            samples, records = g.raycast_counters(reset=True)
+            rc_us = pr["ms"] * 1e3 / max(pr["launches"], 1)
+            rc_bytes = (8.0 * samples + 32.0 * records) / max(args.raycast_reps, 1) + 16.0 * N
+            depth_r = g.download(buf, (H, W), np.float32)
+            hit = depth_r > 0
+            raycast = {"kernel": "k_raycast", "avg_launch_us": round(rc_us, 2), "launches": int(pr["launches"]),
+                       "algorithmic_bytes_per_launch": round(rc_bytes), "achieved": round(rc_bytes / (rc_us * 1e-6) / 1e9, 1) if rc_us > 0 else 0.0,
+                       "frac": round(rc_bytes / (rc_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4) if rc_us > 0 else 0.0,
+                       "samples_per_launch": int(samples // max(args.raycast_reps, 1)), "records_per_launch": int(records // max(args.raycast_reps, 1)),
+                       "hit_fraction": round(float(hit.mean()), 4),
+                       "median_abs_diff_to_input_depth_mm": round(float(np.median(np.abs(depth_r - frames[-1][0])[hit])) * 1e3, 3) if hit.any() else None}
 
     # device n_upd against the oracle's, on the CPU-sample frames at the oracle's poses (filled in below)
     def device_n_upd(i, R, t):
@@ -655,16 +669,17 @@ def main():
     traffic = None
     l2_atomics = None
     traffic_source = None
-    try:
-        is_c3_ = (W, H) == (1280, 960) and abs(float(vs) - 0.005) < 1e-6 and args.trunc == 10.0 and args.hash_capacity_log2 == 25
-        with open(os.path.join(ROOT, "profiles", "pmc_latest_c3.json" if is_c3_ else "pmc_latest.json")) as f:
-            if is_c3_ or ((W, H) == (640, 480) and abs(float(vs) - 0.01) < 1e-6 and args.trunc == 10.0 and args.hash_capacity_log2 == 22):
-                pmc = json.load(f)
-                traffic = pmc.get("traffic_bytes_per_fusion")
-                l2_atomics = round(pmc.get("k_fuse", {}).get("TCC_ATOMIC", 0))
-                traffic_source = "%s (rocprofv3 --pmc, `%s`)" % (pmc.get("source"), pmc.get("command"))
-    except (OSError, ValueError):
-        pass
+    if args.full:
+        try:
+            is_c3_ = (W, H) == (1280, 960) and abs(float(vs) - 0.005) < 1e-6 and args.trunc == 10.0 and args.hash_capacity_log2 == 25
+            with open(os.path.join(ROOT, "profiles", "pmc_latest_c3.json" if is_c3_ else "pmc_latest.json")) as f:
+                if is_c3_ or ((W, H) == (640, 480) and abs(float(vs) - 0.01) < 1e-6 and args.trunc == 10.0 and args.hash_capacity_log2 == 22):
+                    pmc = json.load(f)
+                    traffic = pmc.get("traffic_bytes_per_fusion")
+                    l2_atomics = round(pmc.get("k_fuse", {}).get("TCC_ATOMIC", 0))
+                    traffic_source = "%s (rocprofv3 --pmc, `%s`)" % (pmc.get("source"), pmc.get("command"))
+        except (OSError, ValueError):
+            pass
 
     # what the line is quoted on follows the arguments: only the two single-GPU BASELINE configurations carry their names
     cm = "%gcm" % (float(vs) * 100.0)
@@ -707,6 +722,7 @@ def main():
                     "next_depth_hint": bool(NEXT_HINT),   # gsdf_hint_next_depth_dev in the resident loops (see track_fuse)
                     "parallelism": "replicas x%d (tracked path does not shard)" % world + (
                         " -- ALL RANKS ON ONE GPU (--rccl-double: launch-path test, value is not an N-GPU number)" if args.rccl_double else ""),
+                    "full": bool(args.full),             # --full: the flavours, configurations and replays below were run
                     "value_is": "median of %d timed windows" % len(runs),
                     "value_runs": [round(total_frames / r, 1) for r in runs],
                 "burn_in_windows": len(burn), "burn_in_runs": [round(total_frames / r, 1) for r in burn],
@@ -714,7 +730,7 @@ def main():
                     "max_abs_translation_error_m": round(trans_err, 5), "voxels": voxels,
                     "n_upd_per_frame": round(n_upd_timed / max(n_conv, 1)), "n_hit_per_pass": round(n_hit_timed / max(passes * K, 1)),
                     "n_upd_oracle_checked": n_upd_checked,
-                    "fused_only_fps": round(fused_fps * world, 1),
+                    "fused_only_fps": round(fused_fps * world, 1) if fused_fps is not None else None,
                     # the same K frames handed over as page-locked HOST buffers (upload ahead of the stream + wait + track + fuse)
                     "staged_fps": round(total_frames / float(np.median(staged_runs)), 1) if staged_runs else None,
                     "staged_runs": [round(total_frames / r, 1) for r in staged_runs] if staged_runs else None,
@@ -726,7 +742,7 @@ def main():
                     "c3": extras.get("c3"),
                     "sharded": sharded,
                 },
-                "roofline": {
+                "roofline": None if not args.full else {
                     "bound": "hbm", "kernel": "k_fuse", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
                     "algorithmic_bytes_per_launch": round(alg_bytes), "avg_launch_us": round(fuse_ms * 1e3, 2),

@@ -636,7 +636,7 @@ def test_bench_two_ranks_on_one_gpu(pkg):
     stream + the sharded GT-pose flavour with ONE exchange (gsdf_merge_allreduce_with over gloo: RCCL refuses two ranks on one
     device), one JSON line from rank 0."""
     out = _run_bench(["--gpus", "2", "--single-device", "--dist-backend", "gloo", "--steps", "6", "--warmup", "3", "--repeats", "2",
-                      "--c4-frames", "12", "--raycast-reps", "2", "--cpu-frames", "0"])
+                      "--full", "--c4-frames", "12", "--raycast-reps", "2", "--cpu-frames", "0"])
     assert out["n_gpus"] == 2 and out["steps"] == 6 and out["scaling"] == "weak" and out["value"] > 0
     assert len(out["config"]["value_runs"]) == 2
     sh = out["config"]["sharded"]
@@ -657,7 +657,7 @@ def test_bench_gpus_4_end_to_end_over_the_rccl_double():
     shards on two contexts each, gsdf_merge_allreduce with 4 peers, mesh on rank 0, ONE JSON line from rank 0 -- labelled as the
     double so that it can never pass for a scaling number."""
     fake = _build_fake_rccl()
-    out = _run_bench(["--gpus", "4", "--steps", "10", "--warmup", "3", "--repeats", "2", "--c4-frames", "32", "--rccl-double", fake,
+    out = _run_bench(["--gpus", "4", "--steps", "10", "--warmup", "3", "--repeats", "2", "--full", "--c4-frames", "32", "--rccl-double", fake,
                       "--raycast-reps", "0", "--no-staged", "--rank-timeout", "800"], timeout=900)
     assert out["n_gpus"] == 4 and out["steps"] == 10 and out["value"] > 0 and out["scaling"] == "weak"
     assert "ONE GPU" in out["config"]["parallelism"]
@@ -668,6 +668,21 @@ def test_bench_gpus_4_end_to_end_over_the_rccl_double():
     assert sh["frames_total"] == 4 * 32 and sh["frames_counter_after_merge"] == 4 * 32
     assert sh["voxels_merged"] > sh["voxels_own_shard"] and sh["exchange_blocks"] > 1000 and sh["mesh_faces"] > 1000
     assert out["cpu_baseline"] is None or out["n_gpus"] == 4          # the CPU baseline is an N = 1 item
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_only():
+    """Without --full a run measures `value` and nothing beside it: no flavour, configuration, replay or CPU baseline appears in
+    the line, whatever their own options say."""
+    out = _run_bench(["--steps", "4", "--warmup", "2", "--repeats", "2", "--c4-frames", "8", "--raycast-reps", "2", "--cpu-frames", "2"],
+                     timeout=300)
+    assert out["steps"] == 4 and out["warmup"] == 2 and out["value"] > 0 and out["ms_per_step"] > 0
+    assert out["unit"] == "frames/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    cfg = out["config"]
+    assert cfg["full"] is False and len(cfg["value_runs"]) == 2 and cfg["voxels"] > 0
+    assert out["roofline"] is None and out["cpu_baseline"] is None
+    for k in ("fused_only_fps", "staged_fps", "raycast_us", "streams_per_gpu", "default_window", "c3", "sharded", "n_upd_oracle_checked"):
+        assert cfg[k] is None, (k, cfg[k])
 
 
 # ---- bench.py --dump-outputs ----------------------------------------------------------------------------------------------

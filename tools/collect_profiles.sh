@@ -1,8 +1,8 @@
 #!/bin/bash
 # Collects the evidence behind bench.py's numbers on the GPU box (run through gpurun from the repo root):
 #   tools/collect_profiles.sh <tag>       -> gpurun_out/prof_<tag>/...   (copy what is to be judged into profiles/)
-# 1. plain bench lines: the driver's window (--steps 20 --warmup 5) and the default window;
-# 2. rocprofv3 --kernel-trace --stats over the driver's command (per-kernel table + min/median/p90 + timeline classes);
+# 1. bench lines with --full: the driver's window (--steps 20 --warmup 5) and the default window;
+# 2. rocprofv3 --kernel-trace --stats over the first of them (per-kernel table + min/median/p90 + timeline classes);
 # 3. rocprofv3 --pmc passes over the SAME command, one counter group per pass (FETCH_SIZE and WRITE_SIZE cannot share a pass).
 #   tools/collect_profiles.sh <tag> c3    -> the same for BASELINE configs[2] (1280x960, 5 mm voxels, capacity 2^25: the map is
 #                                            1 GiB of records, outside the Infinity Cache): bench line, kernel trace, PMC passes
@@ -11,7 +11,7 @@ tag=${1:-r02}
 cfg=${2:-c2}
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
-DRV="python $root/bench.py --gpus 1 --steps 20 --warmup 5"
+DRV="python $root/bench.py --gpus 1 --steps 20 --warmup 5 --full"
 PMCJSON=pmc_latest.json
 if [ "$cfg" = "c3" ]; then
   tag=${tag}_c3
@@ -23,13 +23,13 @@ out=$root/gpurun_out/prof_$tag
 mkdir -p $out
 if [ -z "${SKIP_BENCH:-}" ]; then
 $DRV > $out/bench_driver_window.json 2> $out/bench_driver_window.err
-[ "$cfg" = "c3" ] || GSDF_BENCH_DEBUG=1 python $root/bench.py > $out/bench_default.json 2> $out/bench_default.err
+[ "$cfg" = "c3" ] || GSDF_BENCH_DEBUG=1 python $root/bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 rm -rf /tmp/kt && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -o bench -- $DRV --cpu-frames 0 > $out/bench_profiled.json 2> $out/rocprof_kernel_trace.err
 cp $(find /tmp/kt -name '*kernel_stats.csv' | head -1) $out/bench_kernel_stats.csv 2>/dev/null
 python $root/tools/trace_summary.py /tmp/kt > $out/bench_kernel_summary.txt 2>&1
 python $root/tools/trace_timeline.py /tmp/kt > $out/bench_kernel_timeline.txt 2>&1
 # the same trace over the default 200-step window (a quarter of its frames does not converge: 25 passes, no fusion)
-[ "$cfg" = "c3" ] || { rm -rf /tmp/ktd && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ktd -o bench -- python $root/bench.py --cpu-frames 0 > $out/bench_default_profiled.json 2> $out/rocprof_kernel_trace_default.err
+[ "$cfg" = "c3" ] || { rm -rf /tmp/ktd && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ktd -o bench -- python $root/bench.py --full --cpu-frames 0 > $out/bench_default_profiled.json 2> $out/rocprof_kernel_trace_default.err
 python $root/tools/trace_summary.py /tmp/ktd > $out/bench_default_kernel_summary.txt 2>&1; }
 fi
 i=0
@@ -50,10 +50,10 @@ cp $root/gpurun_out/raycast_pmc_$tag.txt $out/raycast_pmc_counters.txt 2>/dev/nu
 # 5. the tracker: per-workgroup phase traces of one frame, one launch per pass (default) and the one-launch optimize() (GSDF_PERSIST=1)
 GSDF_PERSIST=0 python $root/tools/track_trace.py 20 > $out/track_trace_per_pass.txt 2>&1
 GSDF_PERSIST=1 python $root/tools/track_all_trace.py 20 > $out/track_trace_one_launch.txt 2>&1
-GSDF_PERSIST=1 python $root/bench.py --steps 20 --warmup 5 --only-main > $out/bench_one_launch_tracker.json 2> /dev/null
+GSDF_PERSIST=1 python $root/bench.py --steps 20 --warmup 5 --full --only-main > $out/bench_one_launch_tracker.json 2> /dev/null
 # 6. k_fuse and the number of dispatch rounds: frame sizes with 1040 / 1200 / 1536 / 2048 tiles on the 512 workgroup slots
 for wh in "640 416" "640 480" "768 512" "1024 512"; do set -- $wh
-  python $root/bench.py --steps 20 --warmup 5 --only-main --repeats 2 --width $1 --height $2 2>/dev/null | python -c "
+  python $root/bench.py --steps 20 --warmup 5 --full --only-main --repeats 2 --width $1 --height $2 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):
