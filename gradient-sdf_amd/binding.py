@@ -132,6 +132,10 @@ def load(path=None):
         "gsdf_ba_optimize": (C.c_int, [vp, C.c_int, fp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "gsdf_ba_get_poses": (C.c_int, [vp, fp]),
         "gsdf_ba_counters": (C.c_int, [vp, i64p, i64p]),
+        "gsdf_color_compute": (C.c_int, [vp, C.c_int, fp, fp, C.POINTER(C.c_int), i64p]),
+        "gsdf_color_export": (C.c_int, [vp, i32p, fp, C.c_int64, i64p]),
+        "gsdf_color_cloud": (C.c_int, [vp, fp, C.c_int64, i64p]),
+        "gsdf_color_counters": (C.c_int, [vp, i64p, i64p]),
         "gsdf_merge_prepare": (C.c_int, [vp, C.c_int]),
         "gsdf_grow": (C.c_int, [vp, C.c_int]),
         "gsdf_set_auto_grow": (C.c_int, [vp, C.c_int]),
@@ -191,7 +195,8 @@ ABI_SYMBOLS = [
     "gsdf_normals_init", "gsdf_normals_cache", "gsdf_normals_compute", "gsdf_update", "gsdf_update_dev",
     "gsdf_track", "gsdf_track_sampled", "gsdf_hint_next_depth_dev", "gsdf_track_and_fuse_ahead_dev", "gsdf_set_pose", "gsdf_get_pose", "gsdf_track_and_fuse_dev", "gsdf_read_frame_log",
     "gsdf_sync", "gsdf_get_stats", "gsdf_count", "gsdf_export", "gsdf_enable_vis", "gsdf_export_vis",
-    "gsdf_ba_setup", "gsdf_ba_set_loss", "gsdf_ba_energy", "gsdf_ba_solve_pose", "gsdf_ba_solve_dist", "gsdf_ba_optimize", "gsdf_ba_get_poses", "gsdf_ba_counters", "gsdf_grow", "gsdf_set_auto_grow", "gsdf_capacity", "gsdf_merge_from", "gsdf_create_shards", "gsdf_merge_prepare",
+    "gsdf_ba_setup", "gsdf_ba_set_loss", "gsdf_ba_energy", "gsdf_ba_solve_pose", "gsdf_ba_solve_dist", "gsdf_ba_optimize", "gsdf_ba_get_poses", "gsdf_ba_counters",
+    "gsdf_color_compute", "gsdf_color_export", "gsdf_color_cloud", "gsdf_color_counters", "gsdf_grow", "gsdf_set_auto_grow", "gsdf_capacity", "gsdf_merge_from", "gsdf_create_shards", "gsdf_merge_prepare",
     "gsdf_merge_raw", "gsdf_export_raw_dev",
     "gsdf_merge_raw_dev", "gsdf_block_keys_dev", "gsdf_pack_blocks_dev", "gsdf_unpack_blocks_dev",
     "gsdf_merge_allreduce", "gsdf_merge_allreduce_with", "gsdf_rccl_unique_id", "gsdf_rccl_comm_init", "gsdf_rccl_comm_count",
@@ -506,6 +511,51 @@ class GradSdf:
         P = np.zeros((self._ba_n, 16), np.float32)
         self._chk(self.L.gsdf_ba_get_poses(self.h, _fp(P)))
         return P.reshape(self._ba_n, 4, 4)
+
+    # -- ColorUpsampler ------------------------------------------------------------------------------
+    def color_compute(self, n=None, images_bgr=None, poses16=None, frame_idx=None):
+        """gsdf_color_compute: sub-voxel albedo of the voxels near the surface (a snapshot).  None for images / poses / frame_idx
+        = PhotoBA's (gsdf_ba_setup's images and keyframes, its CURRENT poses); n defaults to the keyframes given or PhotoBA's.
+        Returns the number of Hr voxels."""
+        img = None if images_bgr is None else _f32(images_bgr)
+        P = None if poses16 is None else _f32(poses16).reshape(-1, 16)
+        idx = None if frame_idx is None else np.ascontiguousarray(frame_idx, dtype=np.int32)
+        if n is None:
+            n = next((a.shape[0] for a in (img, P, idx) if a is not None), getattr(self, "_ba_n", 0))
+        for a in (img, P, idx):
+            if a is not None and a.shape[0] != n:
+                raise ValueError("images, poses and frame_idx must hold n keyframes")
+        nv = C.c_int64(0)
+        self._chk(self.L.gsdf_color_compute(self.h, int(n), None if img is None else _fp(img), None if P is None else _fp(P),
+                                            None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int)), C.byref(nv)))
+        return nv.value
+
+    def color_export(self):
+        """(keys (n, 3) int32, rows (n, 37) float32 = dist, weight, grad[3], d[8], r[8], g[8], b[8]) in (z, y, x) order"""
+        n = C.c_int64(0)
+        self._chk(self.L.gsdf_color_export(self.h, None, None, 0, C.byref(n)))
+        keys = np.empty((n.value, 3), np.int32)
+        rows = np.empty((n.value, 37), np.float32)
+        if n.value:
+            got = C.c_int64(0)
+            self._chk(self.L.gsdf_color_export(self.h, keys.ctypes.data_as(C.POINTER(C.c_int32)), _fp(rows), n.value, C.byref(got)))
+        return keys, rows
+
+    def color_cloud(self):
+        """extractCloud's rows (m, 9) float32: point, normal, colour in [0, 1]"""
+        n = C.c_int64(0)
+        self._chk(self.L.gsdf_color_cloud(self.h, None, 0, C.byref(n)))
+        rows = np.empty((n.value, 9), np.float32)
+        if n.value:
+            got = C.c_int64(0)
+            self._chk(self.L.gsdf_color_cloud(self.h, _fp(rows), n.value, C.byref(got)))
+        return rows
+
+    def color_counters(self):
+        """(Hr voxels, observations) of the colour snapshot"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._chk(self.L.gsdf_color_counters(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def merge_raw(self, keys, payload_raw):
         k = np.ascontiguousarray(keys, np.int32).reshape(-1, 3)

@@ -677,6 +677,7 @@ void gsdf_destroy(gsdf_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->trace) { (void)hipFree(c->trace); c->trace = nullptr; }      /* after the sync: a running kernel may still write stamps */
+    gsdf_color_release(c);
     prof_collect(c);
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
     for (auto& u : c->uploads) { (void)hipEventSynchronize(u.second); (void)hipEventDestroy(u.second); }
@@ -718,6 +719,7 @@ int gsdf_reset(gsdf_ctx* c) {
         HIP_TRY(hipMemsetAsync(c->blk_counters, 0, (size_t)c->fuse_blocks * 4 * sizeof(unsigned long long), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->merged = false;
+    gsdf_color_drop(c);                                      /* the ColorUpsampler snapshot describes the old map */
     c->grow_forget = true;                                   /* auto-grow's block counts describe the old map (a grown table keeps its size) */
     c->occ_dirty = false;                                    /* the table clear zeroed the filters as well */
     return GSDF_OK;

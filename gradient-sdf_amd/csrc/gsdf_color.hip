@@ -1,0 +1,405 @@
+/*
+ * gsdf_color.hip -- ColorUpsampler (ps_optimizer/ColorUpsampler.h/.cpp) over the HBM voxel table: sub-voxel albedo from the
+ * keyframe images and the coloured point cloud (extractCloud), behind gsdf_color_compute / _export / _cloud (include/gsdf.h).
+ *
+ *   selection   init :143-146         voxels with |dist| < (float)(sqrt(3) vs): rocPRIM select over the slots (as gsdf_ba_compact)
+ *   order       --                    packed (z, y, x) keys of the selection, radix-sorted with their slots (gsdf_sort.hip)
+ *   k_color     computeColor :334-377 8 lanes per Hr voxel (SdfVoxelHr, SdfVoxel.h:83-101), one per sub-voxel
+ *   k_cloud_*   extractCloud :251-330 per-voxel predicate and count, exclusive scan, compaction into 9-float rows
+ *
+ * The result is a snapshot, like the reference's SdfHrMap copy: it lives in buffers of its own, sorted by key, and later
+ * fusion, BA steps or table growth leave it as it is until the next gsdf_color_compute.  The table is only read.
+ */
+#include "gsdf_ctx.h"
+#include "gsdf_interp.h"
+#include "gsdf_kernels.h"
+#include "gsdf_math.h"
+
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_select.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#define GSDF_COLOR_ROW 37            /* dist, weight, grad[3], d[8], r[8], g[8], b[8] */
+
+/* ---- device ---------------------------------------------------------------------------------------------------------- */
+
+/* init :143-146: the voxel exists (w > 0, as ba_load_voxel) and fabsf(dist) < (float)(sqrt(3.) * vs), strict, in float */
+struct color_sel_pred {
+    const unsigned long long* bkeys;
+    const gsdf_payload* vox;
+    float gate;
+    __device__ bool operator()(const uint32_t& slot) const {
+        if (bkeys[slot / GSDF_BLOCK_VOX] == GSDF_KEY_EMPTY) return false;
+        const float2 ws = *reinterpret_cast<const float2*>(vox + slot);        /* w, s */
+        if (!(ws.x > 0.f)) return false;
+        return fabsf(ws.y / ws.x) < gate;
+    }
+};
+
+__global__ __launch_bounds__(256) void k_color_keys(const uint32_t* __restrict__ list, const unsigned long long* __restrict__ bkeys,
+                                                     unsigned long long* __restrict__ keys, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t slot = list[i];
+    keys[i] = gsdf_voxel_key(bkeys[slot / GSDF_BLOCK_VOX], slot % GSDF_BLOCK_VOX);
+}
+
+/* getSubvoxelFloat :208-212, one coordinate: vs * (0.25f * (+-1) + idx) */
+__device__ __forceinline__ float color_centre(float vs, int hi, int idx) { return vs * ((hi ? 0.25f : -0.25f) + (float)idx); }
+
+struct color_args {
+    gsdf_table tab;
+    const uint32_t* slots;            /* the selected slots in (z, y, x) key order */
+    long long n_vox;
+    const uint32_t* vis;
+    int vis_words;
+    int n, W, H;
+    const float* images;              /* n x H x W x 3 BGR */
+    const float* R;                   /* n x 9, row-major */
+    const float* t;                   /* n x 3 */
+    const int* frame_idx;
+    float fx, fy, cx, cy, vs;
+    float* rows;                      /* n_vox x GSDF_COLOR_ROW */
+    unsigned long long* obs;          /* device word: voxel x keyframe observations (added to) */
+};
+
+/* 8 lanes per Hr voxel, lane (i & 7) = sub-voxel i (x from bit 0, y from bit 1, z from bit 2): 8 voxels per wave64.  The keyframe
+ * loop is uniform over the wave: a keyframe counts for a voxel only if all 8 of its sub-voxels project into the image
+ * (getIntensity :181-197), and that is an 8-bit field of one __ballot.  The 8 sub-voxels of a voxel lie a quarter voxel apart,
+ * so their bilinear taps fall on neighbouring pixels and mostly hit the same cache lines. */
+__global__ __launch_bounds__(256) void k_color(color_args a) {
+    const int lane = threadIdx.x & 63, sub = lane & 7, gbase = lane & ~7;
+    const long long item = ((long long)blockIdx.x * 256 + threadIdx.x) >> 3;
+    const bool live = item < a.n_vox;
+    size_t slot = 0;
+    float w = 0.f, dist = 0.f;
+    gsdf_v3 g = { 0.f, 0.f, 0.f };
+    int x = 0, y = 0, z = 0;
+    uint32_t myword = 0u;
+    if (live) {
+        slot = a.slots[item];
+        const unsigned long long bk = a.tab.bkeys[slot / GSDF_BLOCK_VOX];
+        const gsdf_payload p = a.tab.vox[slot];
+        w = p.w; dist = p.s / p.w;                                             /* as ba_load_voxel */
+        g = gsdf_v3{ p.gx, p.gy, p.gz };
+        gsdf_key_unpack(gsdf_voxel_key(bk, (uint32_t)(slot % GSDF_BLOCK_VOX)), &x, &y, &z);
+        if (sub < a.vis_words) myword = a.vis[slot * a.vis_words + sub];     /* the voxel's vis_ words, once per group */
+    }
+    /* SdfVoxelHr(voxel, vs) -- SdfVoxel.h:83-101: grad normalised, d[i] = dist + vs4 * (+-g0 +- g1 +- g2) evaluated left to right
+     * (a - b is a + (-b) exactly, so every sign pattern of :92-99 is (s0 + s1) + s2) */
+    const gsdf_v3 gn = gsdf_normalized3(g);
+    const float vs4 = 0.25f * a.vs;
+    const float s0 = (sub & 1) ? gn.x : -gn.x, s1 = (sub & 2) ? gn.y : -gn.y, s2 = (sub & 4) ? gn.z : -gn.z;
+    const float d = dist + vs4 * ((s0 + s1) + s2);
+    /* getSubvoxelFloat :208-212: vs * (0.25f * corner + idx) */
+    const gsdf_v3 c = { color_centre(a.vs, sub & 1, x), color_centre(a.vs, sub & 2, y), color_centre(a.vs, sub & 4, z) };
+    const gsdf_v3 q = { c.x - gn.x * d, c.y - gn.y * d, c.z - gn.z * d };     /* centre_i - grad d[i] */
+    const float Wf = (float)a.W, Hf = (float)a.H;
+    gsdf_v3 sum = { 0.f, 0.f, 0.f };
+    int count = 0;
+    for (int i = 0; i < a.n; ++i) {                                            /* computeColor :346-365 */
+        const int f = a.frame_idx[i];                                          /* wave-uniform */
+        const int wi = f >> 5;
+        uint32_t word = 0u;
+        if (wi < a.vis_words) {                                                /* ba_visible's rule: bits past the vectors are unset */
+            if (wi < 8) word = (uint32_t)__shfl((int)myword, gbase + wi);
+            else if (live) word = a.vis[slot * a.vis_words + wi];
+        }
+        const bool seen = live && ((word >> (f & 31)) & 1u);
+        if (!__any(seen)) continue;                                            /* wave-uniform skip */
+        const float* Ri = a.R + 9 * i;
+        const float* ti = a.t + 3 * i;
+        /* getIntensity :175: R^T ((centre_i - grad d[i]) - t), summed as ba_project */
+        const gsdf_v3 e = { q.x - ti[0], q.y - ti[1], q.z - ti[2] };
+        const gsdf_v3 p = { gsdf_sum3(Ri[0] * e.x, Ri[3] * e.y, Ri[6] * e.z), gsdf_sum3(Ri[1] * e.x, Ri[4] * e.y, Ri[7] * e.z),
+                            gsdf_sum3(Ri[2] * e.x, Ri[5] * e.y, Ri[8] * e.z) };
+        const float m = (a.fx * p.x) / p.z + a.cx;                             /* :177-178, a true division */
+        const float n = (a.fy * p.y) / p.z + a.cy;
+        /* :181-197: the keyframe is dropped if any m or n is NaN or any sub-voxel falls outside [0,W) x [0,H) -- a NaN fails
+         * every comparison below, so both rules are this one predicate */
+        const bool inside = m >= 0.f && m < Wf && n >= 0.f && n < Hf;
+        const unsigned long long b = __ballot(seen && inside);
+        if (((b >> gbase) & 0xffull) != 0xffull) continue;
+        const ba_img im = { a.W, a.H, a.images + (size_t)i * a.W * a.H * 3 };
+        const gsdf_v3 A = ba_interp(n, m, im);                                 /* interpolateImage(n(i), m(i), img) */
+        sum = gsdf_v3{ sum.x + A.x, sum.y + A.y, sum.z + A.z };
+        ++count;
+    }
+    /* :369-373 and setAlbedo :217-235: (1.f / (float)count) * sum, then std::max(c, 0) and std::min(c, 1) -- a NaN (count 0)
+     * passes both as NaN */
+    const float inv = 1.f / (float)count;
+    float col[3] = { inv * sum.x, inv * sum.y, inv * sum.z };
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        col[k] = (col[k] < 0.f) ? 0.f : col[k];
+        col[k] = (1.f < col[k]) ? 1.f : col[k];
+    }
+    if (live) {
+        float* row = a.rows + (size_t)item * GSDF_COLOR_ROW;
+        if (sub < 5) row[sub] = sub == 0 ? dist : sub == 1 ? w : sub == 2 ? gn.x : sub == 3 ? gn.y : gn.z;
+        row[5 + sub] = d;
+        row[13 + sub] = col[0];
+        row[21 + sub] = col[1];
+        row[29 + sub] = col[2];
+    }
+    /* observations (voxel x keyframe pairs that counted): one atomic per wave */
+    unsigned int o = (live && sub == 0) ? (unsigned int)count : 0u;
+    for (int off = 32; off > 0; off >>= 1) o += (unsigned int)__shfl_xor((int)o, off);
+    if (lane == 0 && o) atomicAdd(a.obs, (unsigned long long)o);
+}
+
+/* extractCloud :259-300 for one Hr voxel of the snapshot: the bit mask of the sub-voxels that are emitted.  The reference's
+ * "seen by at least one keyframe" test (:264-271) is implied by a colour that is not NaN: a voxel no keyframe counted has
+ * count 0 and NaN albedo, and a keyframe counts only where its vis_ bit is set. */
+__device__ __forceinline__ unsigned int color_cloud_mask(const float* row, float vs4, gsdf_v3* nrm) {
+    const gsdf_v3 gg = gsdf_normalized3(gsdf_v3{ row[2], row[3], row[4] });  /* -v.grad.normalized(): normalised a second time */
+    *nrm = gsdf_v3{ -gg.x, -gg.y, -gg.z };
+    if (row[1] < 5) return 0u;                                                 /* :275 */
+    unsigned int mask = 0u;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float d = row[5 + i];
+        const float dx = nrm->x * d, dy = nrm->y * d, dz = nrm->z * d;         /* voxel_normal * v.d.asDiagonal() */
+        if (fabsf(dx) < vs4 && fabsf(dy) < vs4 && fabsf(dz) < vs4 && !isnan(row[13 + i]) && !isnan(row[21 + i]) && !isnan(row[29 + i]))
+            mask |= 1u << i;
+    }
+    return mask;
+}
+__global__ __launch_bounds__(256) void k_cloud_count(const float* __restrict__ rows, size_t n, float vs4, uint32_t* __restrict__ counts) {
+    const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= n) return;
+    gsdf_v3 nrm;
+    counts[v] = (uint32_t)__popc(color_cloud_mask(rows + v * GSDF_COLOR_ROW, vs4, &nrm));
+}
+/* rows9: point centre_i + dvec, normal, colour -- in the snapshot's voxel order, then by sub-voxel index */
+__global__ __launch_bounds__(256) void k_cloud_emit(const unsigned long long* __restrict__ keys, const float* __restrict__ rows, size_t n,
+                                                    float vs, float vs4, const uint32_t* __restrict__ offsets, float* __restrict__ out) {
+    const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= n) return;
+    const float* row = rows + v * GSDF_COLOR_ROW;
+    gsdf_v3 nrm;
+    const unsigned int mask = color_cloud_mask(row, vs4, &nrm);
+    if (!mask) return;
+    int x, y, z;
+    gsdf_key_unpack(keys[v], &x, &y, &z);
+    float* o = out + (size_t)offsets[v] * 9;
+    for (int i = 0; i < 8; ++i) {
+        if (!((mask >> i) & 1u)) continue;
+        const float d = row[5 + i];
+        const float cx = color_centre(vs, i & 1, x), cy = color_centre(vs, i & 2, y), cz = color_centre(vs, i & 4, z);
+        o[0] = cx + nrm.x * d; o[1] = cy + nrm.y * d; o[2] = cz + nrm.z * d;
+        o[3] = nrm.x; o[4] = nrm.y; o[5] = nrm.z;
+        o[6] = row[13 + i]; o[7] = row[21 + i]; o[8] = row[29 + i];
+        o += 9;
+    }
+}
+
+/* ---- host: gsdf_color_* --------------------------------------------------------------------------------------------------- */
+
+struct gsdf_color_state {
+    /* the snapshot */
+    bool valid = false;
+    long long n = 0, obs = 0;
+    float vs = 0.f;
+    unsigned long long* keys = nullptr; size_t keys_cap = 0;       /* packed (z, y, x)-ordered keys */
+    float* rows = nullptr; size_t rows_cap = 0;                    /* GSDF_COLOR_ROW floats per key */
+    long long cloud_n = -1;                                         /* the cloud of the snapshot, made on first request */
+    float* cloud = nullptr; size_t cloud_cap = 0;
+    /* scratch of the compute */
+    float* images = nullptr; size_t images_cap = 0;
+    float* Rt = nullptr; size_t Rt_cap = 0;
+    int* fidx = nullptr; size_t fidx_cap = 0;
+    uint32_t* list = nullptr; size_t list_cap = 0;
+    uint32_t* slots = nullptr; size_t slots_cap = 0;
+    unsigned long long* keys_in = nullptr; size_t keys_in_cap = 0;
+    uint32_t* counts = nullptr; size_t counts_cap = 0;
+    uint32_t* offsets = nullptr; size_t offsets_cap = 0;
+    unsigned char* tmp = nullptr; size_t tmp_cap = 0;              /* rocPRIM scratch */
+    unsigned long long* words = nullptr; size_t words_cap = 0;      /* [0] selected voxels, [1] observations */
+};
+
+namespace {
+
+int cfail(int code, const std::string& msg) { return gsdf_fail(code, msg); }
+
+/* device buffers grow and are kept (a compute per BA run, at sizes that change little) */
+template <class T>
+int color_grow(T** p, size_t* cap, size_t count) {
+    if (count <= *cap && *p) return GSDF_OK;
+    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
+    const size_t want = std::max<size_t>(count, 1);
+    HIP_TRY(hipMalloc((void**)p, want * sizeof(T)));
+    *cap = want;
+    return GSDF_OK;
+}
+#define COLOR_GROW(field, count) do { const int rc_ = color_grow(&S->field, &S->field##_cap, (count)); if (rc_) return rc_; } while (0)
+
+}  // namespace
+
+void gsdf_color_release(gsdf_ctx* c) {
+    gsdf_color_state* S = c->color;
+    if (!S) return;
+    void* ptrs[] = { S->keys, S->rows, S->cloud, S->images, S->Rt, S->fidx, S->list, S->slots, S->keys_in, S->counts, S->offsets, S->tmp, S->words };
+    for (void* p : ptrs) if (p) (void)hipFree(p);
+    delete S;
+    c->color = nullptr;
+}
+void gsdf_color_drop(gsdf_ctx* c) {
+    if (c->color) { c->color->valid = false; c->color->n = 0; c->color->obs = 0; c->color->cloud_n = -1; }
+}
+
+int gsdf_color_compute(gsdf_ctx* c, int n, const float* images_bgr_host, const float* poses16_host, const int* frame_idx,
+                       int64_t* n_voxels) {
+    if (!c) return cfail(GSDF_ERR_INVALID, "null context");
+    if (int rc = gsdf_flush_pending(c)) return rc;
+    if (!c->planes) return cfail(GSDF_ERR_INVALID, "gsdf_normals_init must be called first (image size and intrinsics)");
+    if (c->map_type != GSDF_MAP_GRAD) return cfail(GSDF_ERR_INVALID, "ColorUpsampler needs the Gradient-SDF map (a base-sdf context has no gradient)");
+    if (!c->vis) return cfail(GSDF_ERR_INVALID, "ColorUpsampler needs the vis_ bit-vectors: call gsdf_enable_vis before fusing");
+    if (n < 1 || n > 64) return cfail(GSDF_ERR_INVALID, "bad argument (1..64 keyframes)");
+    const bool from_ba = !images_bgr_host || !poses16_host || !frame_idx;
+    if (from_ba && !c->ba_n) return cfail(GSDF_ERR_INVALID, "NULL images, poses or frame_idx name PhotoBA's: gsdf_ba_setup was not called");
+    if (from_ba && n != c->ba_n) return cfail(GSDF_ERR_INVALID, "NULL images, poses or frame_idx name PhotoBA's: n must equal its keyframe count");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    /* poses and keyframe ids on the host first: the ids are checked, the poses split into R (row-major) and t */
+    std::vector<int> fid((size_t)n);
+    if (frame_idx) std::copy(frame_idx, frame_idx + n, fid.begin());
+    else HIP_TRY(hipMemcpy(fid.data(), c->ba_frame_idx, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    for (int v : fid)
+        if (v < 0) return cfail(GSDF_ERR_INVALID, "frame_idx: keyframe ids must be >= 0");
+    std::vector<float> Rt((size_t)n * 12);
+    for (int i = 0; i < n; ++i)
+        for (int r = 0; r < 3; ++r) {
+            for (int k = 0; k < 3; ++k)
+                Rt[9 * (size_t)i + 3 * r + k] = poses16_host ? poses16_host[16 * (size_t)i + 4 * r + k] : c->ba_R[9 * (size_t)i + 3 * r + k];
+            Rt[9 * (size_t)n + 3 * (size_t)i + r] = poses16_host ? poses16_host[16 * (size_t)i + 4 * r + 3] : c->ba_t[3 * (size_t)i + r];
+        }
+    if (!c->color) c->color = new gsdf_color_state();
+    gsdf_color_state* S = c->color;
+    S->valid = false; S->cloud_n = -1;
+    COLOR_GROW(Rt, Rt.size());
+    COLOR_GROW(fidx, (size_t)n);
+    COLOR_GROW(words, 2);
+    COLOR_GROW(list, c->n_slots);
+    HIP_TRY(hipMemcpyAsync(S->Rt, Rt.data(), Rt.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(S->fidx, fid.data(), fid.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    const float* images = c->ba_images;                                          /* NULL: gsdf_ba_setup's, no second upload */
+    if (images_bgr_host) {
+        const size_t cnt = (size_t)n * c->W * c->H * 3;
+        COLOR_GROW(images, cnt);
+        HIP_TRY(hipMemcpyAsync(S->images, images_bgr_host, cnt * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        images = S->images;
+    }
+    HIP_TRY(hipMemsetAsync(S->words, 0, 2 * sizeof(unsigned long long), c->stream));
+    /* selection: the slots of the kept voxels, in slot order */
+    const float gate = (float)(std::sqrt(3.) * c->voxel_size);                   /* init :143 */
+    const color_sel_pred pred{ c->tab.bkeys, c->tab.vox, gate };
+    size_t bytes = 0;
+    HIP_TRY(rocprim::select(nullptr, bytes, rocprim::counting_iterator<uint32_t>(0u), S->list, S->words, c->n_slots, pred, c->stream));
+    COLOR_GROW(tmp, bytes);
+    bytes = S->tmp_cap;
+    HIP_TRY(rocprim::select(S->tmp, bytes, rocprim::counting_iterator<uint32_t>(0u), S->list, S->words, c->n_slots, pred, c->stream));
+    unsigned long long N = 0;
+    HIP_TRY(hipMemcpyAsync(&N, S->words, sizeof(N), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    /* order: (z, y, x) keys of the selection sorted together with their slots */
+    COLOR_GROW(keys_in, (size_t)N);
+    COLOR_GROW(keys, (size_t)N);
+    COLOR_GROW(slots, (size_t)N);
+    COLOR_GROW(rows, (size_t)N * GSDF_COLOR_ROW);
+    if (N) {
+        hipLaunchKernelGGL(k_color_keys, dim3((unsigned int)((N + 255) / 256)), dim3(256), 0, c->stream, S->list, c->tab.bkeys, S->keys_in, (size_t)N);
+        bytes = 0;
+        HIP_TRY(gsdf_sort_pairs_u64(nullptr, &bytes, S->keys_in, S->keys, S->list, S->slots, (size_t)N, c->stream));
+        COLOR_GROW(tmp, bytes);
+        bytes = S->tmp_cap;
+        HIP_TRY(gsdf_sort_pairs_u64(S->tmp, &bytes, S->keys_in, S->keys, S->list, S->slots, (size_t)N, c->stream));
+        color_args a;
+        a.tab = c->tab; a.slots = S->slots; a.n_vox = (long long)N;
+        a.vis = c->vis; a.vis_words = c->vis_words;
+        a.n = n; a.W = c->W; a.H = c->H;
+        a.images = images; a.R = S->Rt; a.t = S->Rt + 9 * (size_t)n; a.frame_idx = S->fidx;
+        a.fx = c->K[0]; a.fy = c->K[4]; a.cx = c->K[2]; a.cy = c->K[5]; a.vs = c->voxel_size;
+        a.rows = S->rows; a.obs = S->words + 1;
+        hipLaunchKernelGGL(k_color, dim3((unsigned int)((8 * N + 255) / 256)), dim3(256), 0, c->stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    unsigned long long obs = 0;
+    HIP_TRY(hipMemcpyAsync(&obs, S->words + 1, sizeof(obs), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    S->n = (long long)N; S->obs = (long long)obs; S->vs = c->voxel_size;
+    S->valid = true;
+    if (n_voxels) *n_voxels = (int64_t)N;
+    return GSDF_OK;
+}
+
+int gsdf_color_counters(gsdf_ctx* c, int64_t* voxels, int64_t* observations) {
+    if (!c || !voxels || !observations) return cfail(GSDF_ERR_INVALID, "null argument");
+    if (!c->color || !c->color->valid) return cfail(GSDF_ERR_INVALID, "gsdf_color_compute was not called (or the map was reset)");
+    *voxels = c->color->n; *observations = c->color->obs;
+    return GSDF_OK;
+}
+
+int gsdf_color_export(gsdf_ctx* c, int32_t* keys, float* rows, int64_t max_n, int64_t* n) {
+    if (!c) return cfail(GSDF_ERR_INVALID, "null context");
+    if (!c->color || !c->color->valid) return cfail(GSDF_ERR_INVALID, "gsdf_color_compute was not called (or the map was reset)");
+    const gsdf_color_state* S = c->color;
+    if (n) *n = S->n;
+    if (S->n == 0 || max_n <= 0 || (!keys && !rows)) return GSDF_OK;
+    if (max_n < S->n) return cfail(GSDF_ERR_INVALID, "export buffer too small");
+    HIP_TRY(hipSetDevice(c->device));
+    if (rows) HIP_TRY(hipMemcpy(rows, S->rows, (size_t)S->n * GSDF_COLOR_ROW * sizeof(float), hipMemcpyDeviceToHost));
+    if (keys) {
+        std::vector<unsigned long long> hk((size_t)S->n);
+        HIP_TRY(hipMemcpy(hk.data(), S->keys, hk.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < hk.size(); ++i) {
+            int x, y, z;
+            gsdf_key_unpack(hk[i], &x, &y, &z);
+            keys[3 * i] = x; keys[3 * i + 1] = y; keys[3 * i + 2] = z;
+        }
+    }
+    return GSDF_OK;
+}
+
+int gsdf_color_cloud(gsdf_ctx* c, float* rows9, int64_t max_n, int64_t* n) {
+    if (!c) return cfail(GSDF_ERR_INVALID, "null context");
+    if (!c->color || !c->color->valid) return cfail(GSDF_ERR_INVALID, "gsdf_color_compute was not called (or the map was reset)");
+    gsdf_color_state* S = c->color;
+    HIP_TRY(hipSetDevice(c->device));
+    if (S->cloud_n < 0) {                                                      /* predicate, prefix sum, compaction */
+        const size_t N = (size_t)S->n;
+        const float vs4 = (float)(.25 * S->vs);                                /* extractCloud :254 */
+        unsigned long long total = 0;
+        if (N) {
+            COLOR_GROW(counts, N);
+            COLOR_GROW(offsets, N);
+            const dim3 grid((unsigned int)((N + 255) / 256));
+            hipLaunchKernelGGL(k_cloud_count, grid, dim3(256), 0, c->stream, S->rows, N, vs4, S->counts);
+            size_t bytes = 0;
+            HIP_TRY(rocprim::exclusive_scan(nullptr, bytes, S->counts, S->offsets, 0u, N, rocprim::plus<uint32_t>(), c->stream));
+            COLOR_GROW(tmp, bytes);
+            bytes = S->tmp_cap;
+            HIP_TRY(rocprim::exclusive_scan(S->tmp, bytes, S->counts, S->offsets, 0u, N, rocprim::plus<uint32_t>(), c->stream));
+            uint32_t last[2] = { 0u, 0u };
+            HIP_TRY(hipMemcpyAsync(&last[0], S->offsets + N - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(&last[1], S->counts + N - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            total = (unsigned long long)last[0] + last[1];
+            COLOR_GROW(cloud, (size_t)total * 9);
+            hipLaunchKernelGGL(k_cloud_emit, grid, dim3(256), 0, c->stream, S->keys, S->rows, N, S->vs, vs4, S->offsets, S->cloud);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
+        S->cloud_n = (long long)total;
+    }
+    if (n) *n = S->cloud_n;
+    if (S->cloud_n == 0 || max_n <= 0 || !rows9) return GSDF_OK;
+    if (max_n < S->cloud_n) return cfail(GSDF_ERR_INVALID, "cloud buffer too small");
+    HIP_TRY(hipMemcpy(rows9, S->cloud, (size_t)S->cloud_n * 9 * sizeof(float), hipMemcpyDeviceToHost));
+    return GSDF_OK;
+}

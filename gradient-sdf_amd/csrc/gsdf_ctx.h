@@ -25,6 +25,9 @@ struct gsdf_ctx;
 int gsdf_flush_pending(gsdf_ctx* c);               /* gsdf_capi.hip: launch the deferred GT-pose fusion, if one waits */
 int gsdf_grow_impl(gsdf_ctx* c, int new_capacity_log2);      /* gsdf_merge.hip: rehash into a larger table */
 void gsdf_enqueue_block_count(gsdf_ctx* c, unsigned int tag);   /* gsdf_merge.hip: existing blocks | tag << 32 -> pinned words progress[4..5] */
+struct gsdf_color_state;                           /* gsdf_color.hip: the ColorUpsampler snapshot and its scratch */
+void gsdf_color_release(gsdf_ctx* c);              /* frees it (gsdf_destroy) */
+void gsdf_color_drop(gsdf_ctx* c);                 /* forgets the snapshot, keeps the buffers (gsdf_reset) */
 
 inline int gsdf_fail(int code, const std::string& msg) {
     g_gsdf_err = msg;
@@ -129,6 +132,7 @@ struct gsdf_ctx {
     int ba_mean_on = 1;                            /* GSDF_BA_MEAN_CACHE (read by gsdf_ba_setup) */
     bool ba_mean_valid = false;                    /* ... at the very state (poses, distances, gate list) the next pose sweep will see */
     long long ba_last_voxels = 0, ba_last_obs = 0; /* what the last energy sweep read back counted (gsdf_ba_counters) */
+    gsdf_color_state* color = nullptr;             /* ColorUpsampler (gsdf_color_compute): created on first use */
     unsigned int track_serial = 0;                 /* optimize() call counter */
     volatile unsigned int* progress = nullptr;     /* pinned host words written by the tracker epilogue */
     unsigned int* progress_dev = nullptr;

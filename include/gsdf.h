@@ -237,6 +237,45 @@ int gsdf_ba_get_poses(gsdf_ctx* c, float* poses16_host);
  * (measurement only; the reference has no counterpart) */
 int gsdf_ba_counters(gsdf_ctx* c, int64_t* voxels, int64_t* observations);
 
+/* ColorUpsampler (ps_optimizer/ColorUpsampler.h/.cpp with SdfVoxelHr, sdf_voxel/SdfVoxel.h:61-112): sub-voxel albedo of the
+ * voxels near the surface, averaged over the keyframes that see them, and the coloured point cloud.  main_photo_ba.cpp:300-311
+ * runs it after PhotoBA.
+ *
+ * gsdf_color_compute builds the result from the table as it is now, a SNAPSHOT like the reference's SdfHrMap copy: later
+ * fusion, BA steps or table growth leave it as it is until the next compute; gsdf_reset drops it.  The table is only read.
+ *  - selection (init :143-146): a voxel is kept iff it exists and fabsf(dist) < (float)(sqrt(3.0) * vs), strict, in float; dist is
+ *    s / w as the BA sweeps read it, so distances refined by gsdf_ba_solve_dist / gsdf_ba_optimize are used.
+ *  - Hr voxel (SdfVoxel.h:83-101): grad = normalized(g); d[i] = dist + vs4 * (+-g0 +- g1 +- g2) in the order of :92-99,
+ *    vs4 = 0.25f * vs; sub-voxel i takes x from bit 0, y from bit 1, z from bit 2; its centre is vs * (0.25f * corner_i + idx)
+ *    (getSubvoxelFloat :208-212).
+ *  - per keyframe (computeColor :334-377, getIntensity :168-204): it counts only if the voxel's vis_ bit frame_idx[i] is set
+ *    (PhotoBA's rule: ids past the vectors are unset).  Point = R^T ((centre_i - grad d[i]) - t); m = (fx x) / z + cx,
+ *    n = (fy y) / z + cy (a true division).  The keyframe is skipped for all 8 sub-voxels if any m or n is NaN or any sub-voxel
+ *    falls outside [0,W) x [0,H); otherwise interpolateImage(n, m) -- PhotoBA's sampling -- is added to per-channel float
+ *    sums, and the voxel's one observation count grows by one.  The reference's vis_ resize to frame_idx.back() + 1 (:159) makes
+ *    a frame_idx that is not ascending undefined behaviour there; here any order of ids >= 0 is accepted.
+ *  - albedo (:369-373, setAlbedo :217-235): c = (1.f / (float)count) * sum clamped to [0, 1]; count 0 gives NaN, which stays NaN
+ *    through the clamp.
+ * images_bgr_host: n x H x W x 3 floats (BGR, [0,1]) or NULL = the images of gsdf_ba_setup (no second upload).
+ * poses16_host: n row-major 4x4 camera-to-world poses, or NULL = PhotoBA's CURRENT poses (gsdf_ba_get_poses).  The reference
+ *   colours with the pre-BA key poses (setPoses copies them, PhotometricOptimizer.h:148-151, main_photo_ba.cpp:295,300) while
+ *   the distances are the refined ones: pass those poses to reproduce it.
+ * frame_idx: n keyframe ids (vis_ bits), or NULL = those of gsdf_ba_setup.
+ * Any NULL needs an earlier gsdf_ba_setup with the same n.  GSDF_ERR_INVALID: a base-sdf context, no gsdf_enable_vis, n outside
+ * 1..64, a NULL without gsdf_ba_setup, a negative keyframe id.  *n_voxels (nullable) = Hr voxels (getVoxelNumber). */
+int gsdf_color_compute(gsdf_ctx* c, int n, const float* images_bgr_host, const float* poses16_host, const int* frame_idx,
+                       int64_t* n_voxels);
+/* the snapshot in (z, y, x) key order (gsdf_export(sorted = 1)): keys n x 3, rows n x 37 = dist, weight, grad[3] (normalised),
+ * d[8], r[8], g[8], b[8].  *n = Hr voxels; NULL keys and rows only report it.  GSDF_ERR_INVALID before a compute. */
+int gsdf_color_export(gsdf_ctx* c, int32_t* keys, float* rows, int64_t max_n, int64_t* n);
+/* extractCloud (:251-330): one row of 9 floats -- point centre_i + dvec, normal, colour in [0,1] -- per sub-voxel of a voxel
+ * seen by a keyframe with weight >= 5, where n = -normalized(grad) (normalised again, as the reference does), dvec = n * d[i],
+ * all three |dvec| < vs4 and no colour channel NaN.  Rows follow the snapshot's voxel order, then the sub-voxel index (the
+ * reference's order is its hash map's).  *n = rows; NULL rows9 only reports it.  GSDF_ERR_INVALID before a compute. */
+int gsdf_color_cloud(gsdf_ctx* c, float* rows9, int64_t max_n, int64_t* n);
+/* Hr voxels and observations (voxel x keyframe pairs that counted) of the snapshot (measurement only) */
+int gsdf_color_counters(gsdf_ctx* c, int64_t* voxels, int64_t* observations);
+
 /* additive merge of raw sums into this table (frame-sharded fusion) */
 int gsdf_merge_raw(gsdf_ctx* c, const int32_t* keys, const float* payload_raw, int64_t n);
 
