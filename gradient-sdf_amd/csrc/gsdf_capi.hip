@@ -94,6 +94,27 @@ static int fuse_far_table(const gsdf_ctx* c) {
     return c->progress && c->progress[3] * 16u > (unsigned int)c->fuse_blocks ? 1 : 0;
 }
 
+/* the spin-wait hint of an x86 host; elsewhere the core is given away */
+static inline void cpu_relax() {
+#if defined(__x86_64__) || defined(__i386__)
+    __builtin_ia32_pause();
+#else
+    std::this_thread::yield();
+#endif
+}
+/* Polls until done() holds: spins briefly (what the host waits for takes ~50 us), then yields the core between looks; bounded by
+ * TIME, not by iterations.  false = gave up after limit_s seconds */
+template <class Done>
+static bool spin_until(Done done, double limit_s) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (long spin = 0; !done(); ++spin) {
+        if (spin < 4096) { cpu_relax(); continue; }
+        if ((spin & 63) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > limit_s) return false;
+        std::this_thread::yield();
+    }
+    return true;
+}
+
 /* Auto-grow (gsdf_set_auto_grow): called at the top of the frame entries (gsdf_update_dev, gsdf_track_and_fuse_dev).
  *
  * The table is doubled once 45 % of its block entries are in use (the probe budget runs out near 95 %).  The load is the
@@ -146,13 +167,7 @@ static int auto_grow_step(gsdf_ctx* c) {
          * entry while the estimate is low), so `seen` cannot pass grow_last_enq (with a small GSDF_GROW_MAX_LAG the
          * old target k - seen <= lag / 2 was unreachable and the loop spun out its whole timeout on every entry) */
         const int target = std::max(c->grow_max_lag / 2, (int)(k - c->grow_last_enq));
-        const auto t0 = std::chrono::steady_clock::now();
-        for (long spin = 0; (int)(k - seen) > target; ++spin) {
-            look(cnt, seen);
-            if (spin < 4096) { __builtin_ia32_pause(); continue; }
-            if ((spin & 63) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) break;
-            std::this_thread::yield();
-        }
+        spin_until([&] { look(cnt, seen); return (int)(k - seen) <= target; }, 2.0);
         uncovered = k - seen + 1;
     }
     const bool safe = c->grow_counts_seen >= 2 && (int)uncovered <= c->grow_max_lag + 1 &&
@@ -200,18 +215,27 @@ int launch_fuse(gsdf_ctx* c, const float* depth_dev, const float* nrm, const gsd
             c->fuse_tag = 1;
             HIP_TRY(hipMemsetAsync(c->tile_flags, 0, (size_t)c->fuse_blocks * sizeof(unsigned int), c->stream));
         }
-        gsdf_launch_fuse(c->stream, c->geom(), c->ncache(), depth_dev, nrm, nrm + N, nrm + 2 * N, pose,
-                         use_dev_pose, c->tab, c->st, c->blk_counters, c->deferred, c->deferred_count,
-                         c->deferred_cap, c->fuse_tag, c->tile_flags, c->tile_order, c->frame_log, c->frame_log_cap, c->vis, c->vis_words,
-                         c->debug & 0xFFFF, c->fuse_ticket,
-                         /* long deferred lists lately (the note lags by a launch or two: a hint, not a condition) */
-                         c->progress && c->progress[2] > 8192u ? 1 : 0, c->progress ? c->progress_dev + 2 : nullptr,
-                         /* many tiles did not fit the small LDS table lately (far geometry): the kernel with the larger one.
-                          * Like the note above a hint that lags by a launch or two, never a condition for correctness; the
-                          * caller read it once for the whole frame entry (fuse_far_table) */
-                         far_table, head,
-                         next_depth, next_nrm, next_nrm ? next_nrm + N : nullptr, next_nrm ? next_nrm + 2 * N : nullptr, c->win,
-                         stats_of(c, nrm), next_nrm ? stats_of(c, next_nrm) : nullptr, next_token);
+        gsdf_fuse_launch f;
+        f.g = c->geom(); f.nc = c->ncache();
+        f.depth = depth_dev; f.nx = nrm; f.ny = nrm + N; f.nz = nrm + 2 * N; f.tile_stats = stats_of(c, nrm);
+        f.pose = pose; f.use_dev_pose = use_dev_pose;
+        f.tab = c->tab; f.st = c->st; f.blk_counters = c->blk_counters;
+        f.deferred = c->deferred; f.deferred_count = c->deferred_count; f.deferred_cap = c->deferred_cap;
+        f.tag = c->fuse_tag; f.tile_flags = c->tile_flags; f.tile_order = c->tile_order; f.ticket = c->fuse_ticket;
+        f.log_rows = c->frame_log; f.max_rows = c->frame_log_cap; f.vis = c->vis; f.vis_words = c->vis_words;
+        f.debug = c->debug & 0xFFFF;
+        /* long deferred lists lately (the note lags by a launch or two: a hint, not a condition) */
+        f.resolve_follows = c->progress && c->progress[2] > 8192u ? 1 : 0;
+        f.host_note = c->progress ? c->progress_dev + 2 : nullptr;
+        /* many tiles did not fit the small LDS table lately (far geometry): the kernel with the larger one.  Like the note
+         * above a hint that lags by a launch or two, never a condition for correctness; the caller read it once for the whole
+         * frame entry (fuse_far_table) */
+        f.far_table = far_table;
+        f.head = head;
+        f.next_depth = next_depth; f.next_nx = next_nrm; f.next_ny = next_nrm ? next_nrm + N : nullptr; f.next_nz = next_nrm ? next_nrm + 2 * N : nullptr;
+        f.next_tile_stats = next_nrm ? stats_of(c, next_nrm) : nullptr; f.next_token = next_token;
+        f.win = c->win;
+        gsdf_launch_fuse(c->stream, f);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(GSDF_ERR_HIP, std::string("fusion launch: ") + hipGetErrorString(e));
@@ -219,24 +243,229 @@ int launch_fuse(gsdf_ctx* c, const float* depth_dev, const float* nrm, const gsd
 }
 
 /* normals (unless the frame's were computed beside its first tracker pass: normals_done) + fusion, in stream order */
-int enqueue_fuse(gsdf_ctx* c, const float* depth_dev, const gsdf_pose_arg& pose, int use_dev_pose, int far_table, bool normals_done, int set,
-                 const float* next_depth, const gsdf_fuse_head* head, int next_set, unsigned int next_token) {
+int enqueue_fuse(gsdf_ctx* c, const float* depth_dev, const gsdf_pose_arg& pose, int use_dev_pose, int far_table, bool normals_done,
+                 const gsdf_frame_route& route = gsdf_frame_route(), const gsdf_fuse_head* head = nullptr) {
     const size_t N = (size_t)c->W * c->H;
     /* tracked frames: set 2, filled beside the first tracker passes -- or the set the PREVIOUS frame's fusion filled in its
      * tail (gsdf_hint_next_depth_dev) */
-    float* nrm = c->normals + (size_t)set * 3 * N;
+    float* nrm = c->normals + (size_t)route.fuse_set * 3 * N;
+    const float* next_depth = route.hint;
     if (!normals_done) {
-        nrm = c->normals + (size_t)c->nrm_parity * 3 * N;
-        c->nrm_parity ^= 1;
-        c->nrm_ready_depth = nullptr;                  /* (sets 0 / 1 are also where a hinted frame's normals wait) */
+        nrm = c->normals + (size_t)c->ahead.take_gt_set() * 3 * N;
         prof_scope ps(c, 0);
         gsdf_launch_normals(c->stream, c->geom(), c->win, c->ncache(), depth_dev, nrm, nrm + N, nrm + 2 * N, nullptr, nullptr, stats_of(c, nrm));
         next_depth = nullptr;
     }
     /* gsdf_hint_next_depth_dev: the launch's last workgroups compute NormalEstimator::compute of the NEXT frame into set
      * next_set -- if the launch's gate is open -- and leave next_token in st->nrm_token */
-    float* next_nrm = next_depth ? c->normals + (size_t)next_set * 3 * N : nullptr;
-    return launch_fuse(c, depth_dev, nrm, pose, use_dev_pose, far_table, next_depth, next_nrm, head, next_token);
+    float* next_nrm = next_depth ? c->normals + (size_t)route.next_set * 3 * N : nullptr;
+    return launch_fuse(c, depth_dev, nrm, pose, use_dev_pose, far_table, next_depth, next_nrm, head, route.next_token);
+}
+
+/* The end of a batch, seen from the host: *ended = 1 optimize() ended, 0 = the head of launch `last` ran and it has not ended.
+ * Follows the progress word; if the device is far behind (2 s), waits for it properly. */
+int batch_ended(gsdf_ctx* c, unsigned int serial, int last, int* ended) {
+    *ended = -1;
+    spin_until([&] {
+        const gsdf_progress p = gsdf_progress_decode(c->progress[0]);
+        if (p.serial == serial && (p.done || p.passes >= last)) *ended = p.done ? 1 : 0;
+        return *ended >= 0;
+    }, 2.0);
+    if (*ended < 0) {
+        gsdf_dev_state s;
+        if (hipMemcpyAsync(&s, c->st, sizeof(s), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess)
+            return fail(GSDF_ERR_HIP, "tracking: device state read failed");
+        *ended = s.done;
+    }
+    return GSDF_OK;
+}
+
+/* The frame's normals tiles ride in its first launches: nrm_split per cent in launch 0, nrm_split2 in launch 1, the rest
+ * in launch 2.  Launch 1 always exists (it is at least the head of pass 0), launch 2 when the first batch has three
+ * launches and optimize() may take two passes.  Next to the one tracker workgroup per CU a launch hides a share of the
+ * tiles; launch 0 has no head and ends early, so it takes the smallest one.  Tile 0 (it resets the frame's deferred list)
+ * stays in launch 0.
+ * The tiles [*lo, *hi) of launch k, or false = none.  nl: tracker launches of the batch (of the first one: the fusion launch may
+ * stand in for its last one, no riders there; later batches: 3); batch: its length as planned. */
+bool normals_tile_split(int tiles, int k, int nl, int iters, int batch, int nrm_split, int nrm_split2, int* lo, int* hi) {
+    if (k > 2) return false;
+    const bool three = iters >= 2 && batch >= 3 && nl >= 3;
+    const int b1 = nl >= 2 ? std::max(1, tiles * nrm_split / 100) : tiles;
+    const int b2 = three ? std::min(tiles, std::max(b1, tiles * (nrm_split + nrm_split2) / 100)) : tiles;
+    *lo = k == 0 ? 0 : k == 1 ? b1 : b2;
+    *hi = k == 0 ? b1 : k == 1 ? b2 : tiles;
+    return *hi > *lo && (k < 2 || three);
+}
+
+/* one frame on its way through enqueue_track */
+struct track_frame {
+    gsdf_ctx* c;
+    const float* depth;                  /* the frame, or the compaction of its sampled pixels ... */
+    gsdf_frame_geom g;                   /* ... and the pixel grid that goes with it */
+    int iters;
+    bool fuse_after;                     /* the Scan3D loop body: the frame's fusion, gated on the device, behind its passes */
+    int far;                             /* fuse_far_table, read once for the frame */
+    bool new_route;                      /* the round-6 steps are taken (see track_route) */
+    gsdf_frame_route route;
+    bool adaptive;
+    gsdf_track_params tp;
+    gsdf_normals_job nj;
+
+    /* queues the frame's fusion (main_scan_3d.cpp:261-265), optionally with the closing head of optimize() in it */
+    int queue_fusion(const gsdf_fuse_head* head = nullptr) const {
+        gsdf_pose_arg unused;
+        std::memset(&unused, 0, sizeof(unused));
+        return enqueue_fuse(c, depth, unused, 1, far, iters > 0, route, head);
+    }
+};
+
+/* optimize_sampled(depth, K, sampling) -- RigidPointOptimizer.cpp:62: the pixels (x, y) = (i * s, j * s).  They are
+ * compacted into their own image (so that the pass kernel's coalesced pixel -> lane mapping serves them unchanged) and the
+ * passes run on the grid of sampled pixels; k_track_pass<true> turns a grid index back into the pixel coordinate. */
+int compact_sampled(track_frame& f, int sampling) {
+    gsdf_ctx* c = f.c;
+    if (f.fuse_after) return fail(GSDF_ERR_INVALID, "the frame loop tracks every pixel (RigidPointOptimizer.h:69-72)");
+    const int Ws = (c->W + sampling - 1) / sampling, Hs = (c->H + sampling - 1) / sampling;
+    if (!c->depth_sampled) HIP_TRY(hipMalloc((void**)&c->depth_sampled, (size_t)((c->W + 1) / 2) * ((c->H + 1) / 2) * sizeof(float)));
+    gsdf_launch_subsample(c->stream, f.depth, c->W, c->H, sampling, c->depth_sampled);
+    f.depth = c->depth_sampled;
+    f.g.W = Ws; f.g.H = Hs;
+    return GSDF_OK;
+}
+
+/* Which route the frame takes (gsdf_lookahead::consume has the look-ahead side of it).
+ * Both round-6 steps -- the next frame's normals in the fusion's tail, the fusion launch standing in for the first batch's last
+ * tracker launch -- pay where optimize() ends within the first batch and the fusion RUNS behind it.  Frames that converge late or
+ * never come in stretches (the reference's tracker cycles on them), and there the extra workgroups only look at a closed gate
+ * and the stand-in's head is followed by a head-less launch anyway (measured: -1 ... -2 % on the bench's default window): the
+ * host takes the old route while the last tracked frame whose end it KNOWS needed more than the first batch (a hint for the
+ * hint: the progress word of that frame's heads, read without waiting -- in such a stretch the host has just waited for it). */
+void track_route(track_frame& f) {
+    gsdf_ctx* c = f.c;
+    const bool ahead_ok = f.fuse_after && !c->profiling && f.iters > 0;
+    if (f.fuse_after && c->progress) c->ahead.note_progress(c->progress[0]);
+    /* ... and not while the fusion uses the larger LDS table (far geometry): that instantiation with the normals role is at the
+     * register limit and moves its records unpaired, with the head it spills -- both cost more than the step saves.  The choice is
+     * read ONCE here and handed to every fusion launch of this frame: the word it comes from is written by the device while the
+     * host runs, and a second read could pick the larger table for a launch that carries the normals role or the head. */
+    f.far = fuse_far_table(c);
+    f.new_route = ahead_ok && !c->ahead.prev_slow && !f.far;
+    f.route = c->ahead.consume(f.depth, ahead_ok, f.new_route);
+}
+
+/* the per-launch parameters of the frame's passes and the job of the normals riders; takes the frame's serial */
+void track_jobs(track_frame& f, float conv, float damping, int sampling) {
+    gsdf_ctx* c = f.c;
+    std::memset(&f.nj, 0, sizeof(f.nj));
+    if (f.fuse_after) {                  /* the frame's normals ride along with its first passes (unless computed ahead: ride_token) */
+        const size_t N = (size_t)c->W * c->H;
+        f.nj.nc = c->ncache();
+        f.nj.nx = c->normals + (size_t)(3 * f.route.fuse_set) * N; f.nj.ny = f.nj.nx + N; f.nj.nz = f.nj.nx + 2 * N;    /* set 2, or the hinted one */
+        f.nj.token = f.route.ride_token;
+        f.nj.deferred_count = c->deferred_count;
+        f.nj.stats = stats_of(c, f.nj.nx);
+        f.nj.r = c->win / 2; f.nj.ntx = 0;
+        f.nj.tile_first = 0; f.nj.tile_count = 0;
+    }
+    gsdf_track_params& tp = f.tp;
+    tp.max_passes = f.iters;
+    tp.conv_sq = conv * conv;                                /* RigidOptimizer.h:72 */
+    tp.damping = damping;
+    c->track_serial = (c->track_serial + 1u) & 0xFFFFu;
+    if (c->track_serial == 0) c->track_serial = 1;
+    tp.serial = c->track_serial;
+    f.adaptive = c->adaptive && c->progress;
+    /* (the last launch index of this frame's first batch) */
+    if (f.fuse_after) c->ahead.tracked(tp.serial, std::min(f.iters, (f.adaptive ? c->first_batch : f.iters + 1) - 1));
+    tp.progress = f.adaptive ? c->progress_dev : nullptr;
+    tp.debug = c->debug >> 16;
+    tp.n_track_blocks = c->track_blocks;
+    tp.sampling = sampling;
+    tp.head_done = 0;
+}
+
+/* the whole optimize() as one launch; the frame's fusion, gated on the device by done && converged, right behind it */
+int track_one_launch(track_frame& f) {
+    gsdf_ctx* c = f.c;
+    f.tp.pass_index = 0;
+    f.tp.rot = 0;
+    f.tp.progress = c->progress_dev;
+    {
+        prof_scope ps(c, 2);
+        gsdf_launch_track_all(c->stream, f.g, f.depth, c->tab, c->st, c->track_rows, c->track_abort, c->track_blocks, f.tp,
+                              f.fuse_after ? &f.nj : nullptr);
+    }
+    if (f.fuse_after) {
+        const int rc = f.queue_fusion();
+        if (rc) return rc;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GSDF_ERR_HIP, std::string("tracking launch: ") + hipGetErrorString(e));
+    return GSDF_OK;
+}
+
+/* optimize() as batches of per-pass launches, the host following the device between them (see enqueue_track) */
+int track_batched(track_frame& f, int base) {
+    gsdf_ctx* c = f.c;
+    gsdf_track_params& tp = f.tp;
+    const int iters = f.iters, tiles = gsdf_normals_tiles(c->W, c->H);
+    int k = 0, batch_no = 0;
+    int batch = f.adaptive ? c->first_batch : iters + 1;
+    /* The frame's first fusion launch stands in for the LAST tracker launch of the first batch (k_fuse<.., HEAD>): that launch's
+     * head -- for the usual frame the closing one of optimize() -- runs in workgroup 0 of the fusion launch, which every other
+     * workgroup of it follows; a launch and a kernel boundary less per frame.  If optimize() has not ended with that head the
+     * next batch starts with a tracker launch of the same index that skips its head (head_done).  Not in event-timed replays:
+     * what bench.py quotes as k_fuse's duration is the fusion work alone. */
+    const bool fuse_head = f.new_route && f.adaptive && c->fuse_head;
+    bool headless = false;                                   /* the next launch's head was performed by a fusion launch */
+    while (k <= iters) {
+        const int last = std::min(iters, k + batch - 1);
+        const bool stand_in = fuse_head && batch_no == 0 && last >= 1;
+        const int nl = batch_no == 0 ? (stand_in ? last : last + 1) : 3;   /* tracker launches of the batch, as normals_tile_split counts them */
+        for (; k <= last; ++k) {
+            if (stand_in && k == last) continue;             /* its head is the fusion launch's */
+            tp.pass_index = k;
+            tp.head_done = headless ? 1 : 0;
+            headless = false;
+            tp.rot = c->track_rot;
+            c->track_rot = (c->track_rot + 1u) % 3u;          /* kept in [0, 3): no discontinuity at wrap-around */
+            const gsdf_normals_job* job = nullptr;
+            int lo = 0, hi = 0;
+            if (f.fuse_after && normals_tile_split(tiles, k, nl, iters, batch, c->nrm_split, c->nrm_split2, &lo, &hi)) {
+                f.nj.tile_first = lo; f.nj.tile_count = hi - lo; job = &f.nj;
+            }
+            prof_scope ps(c, 2);
+            gsdf_launch_track_pass(c->stream, f.g, f.depth, c->tab, c->st, c->partials, c->track_blocks, tp, job, base);
+        }
+        /* The fusion is queued behind the FIRST batch unseen (the usual frame ends there and must not wait for the host) and
+         * behind the last one (nothing follows it).  Behind the batches in between it would nearly always be a gated launch
+         * that finds optimize() still running -- 3 us each, 3 per frame that never converges -- so there it is queued only
+         * once the progress word says that optimize() has ended (the frame that converges late pays the host's look). */
+        bool fuse_queued = false;
+        if (f.fuse_after && (batch_no == 0 || last == iters || !c->lazy_fuse)) {
+            gsdf_fuse_head hd;
+            std::memset(&hd, 0, sizeof(hd));
+            if (stand_in) {
+                hd.k = last;
+                hd.rot_prev = (c->track_rot + 2u) % 3u;      /* the buffer the last launch issued (pass last - 1) accumulated into */
+                hd.conv_sq = tp.conv_sq; hd.damping = tp.damping; hd.max_passes = tp.max_passes;
+                hd.serial = tp.serial; hd.progress = tp.progress; hd.rows = c->partials; hd.debug = tp.debug;
+            }
+            const int rc = f.queue_fusion(stand_in ? &hd : nullptr);
+            if (rc) return rc;
+            fuse_queued = true;
+        }
+        ++batch_no;
+        if (last == iters) break;                            /* the head-only launch always ends optimize() */
+        int ended = 0;
+        const int rc = batch_ended(c, tp.serial, last, &ended);
+        if (rc) return rc;
+        if (ended) return f.fuse_after && !fuse_queued ? f.queue_fusion() : GSDF_OK;
+        if (stand_in) { k = last; headless = true; }         /* launch `last` comes now, without the head the fusion launch performed */
+        batch = c->next_batch;
+    }
+    return GSDF_OK;
 }
 
 /* RigidPointOptimizer::optimize_sampled as a chain of per-pass launches.  The convergence test, the pose update
@@ -250,207 +479,25 @@ int enqueue_fuse(gsdf_ctx* c, const float* depth_dev, const gsdf_pose_arg& pose,
  * done, passes) and only issues a further batch if the optimisation has not ended by the last head of the
  * previous one.  Correctness never depends on what the host sees: a late or lost observation only costs empty
  * launches. */
-int enqueue_fuse(gsdf_ctx* c, const float* depth_dev, const gsdf_pose_arg& pose, int use_dev_pose, int far_table, bool normals_done, int set = 2,
-                 const float* next_depth = nullptr, const gsdf_fuse_head* head = nullptr, int next_set = 0, unsigned int next_token = 0u);
-
-/* 1 = optimize() ended, 0 = the head of launch `last` ran and it has not ended, -1 = gave up waiting */
-int follow_progress(gsdf_ctx* c, unsigned int serial, int last) {
-    /* a batch takes ~50 us: spin briefly, then yield the core between looks; bounded by TIME (2 s), not by iterations */
-    const auto t0 = std::chrono::steady_clock::now();
-    for (long spin = 0;; ++spin) {
-        const unsigned int w = c->progress[0];
-        if ((w >> 16) == serial) {
-            if (w & 0x8000u) return 1;
-            if ((int)(w & 0x7FFFu) >= last) return 0;
-        }
-        if (spin < 4096) { __builtin_ia32_pause(); continue; }
-        if ((spin & 63) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 2.0) return -1;
-        std::this_thread::yield();
-    }
-}
-
 int enqueue_track(gsdf_ctx* c, const float* depth_dev, int iters, float conv, float damping, bool fuse_after, int sampling = 1) {
-    gsdf_frame_geom g = c->geom();
+    track_frame f;
+    f.c = c; f.depth = depth_dev; f.g = c->geom(); f.iters = iters; f.fuse_after = fuse_after;
     if (sampling > 1) {
-        /* optimize_sampled(depth, K, sampling) -- RigidPointOptimizer.cpp:62: the pixels (x, y) = (i * s, j * s).  They are
-         * compacted into their own image (so that the pass kernel's coalesced pixel -> lane mapping serves them unchanged) and the
-         * passes run on the grid of sampled pixels; k_track_pass<true> turns a grid index back into the pixel coordinate. */
-        if (fuse_after) return fail(GSDF_ERR_INVALID, "the frame loop tracks every pixel (RigidPointOptimizer.h:69-72)");
-        const int Ws = (c->W + sampling - 1) / sampling, Hs = (c->H + sampling - 1) / sampling;
-        if (!c->depth_sampled) HIP_TRY(hipMalloc((void**)&c->depth_sampled, (size_t)((c->W + 1) / 2) * ((c->H + 1) / 2) * sizeof(float)));
-        gsdf_launch_subsample(c->stream, depth_dev, c->W, c->H, sampling, c->depth_sampled);
-        depth_dev = c->depth_sampled;
-        g.W = Ws; g.H = Hs;
+        const int rc = compact_sampled(f, sampling);
+        if (rc) return rc;
     }
-    gsdf_pose_arg unused;
-    std::memset(&unused, 0, sizeof(unused));
-    /* gsdf_hint_next_depth_dev: (1) this frame's normals may already lie in set 0 / 1 -- the previous frame's fusion computed them
-     * in its tail IF IT RAN (a fusion whose gate stays closed does not: its tail is not idle, the tiles would run in the open);
-     * this frame's riders are queued as ever and leave at once when they find the frame's token in st->nrm_token; (2) every
-     * fusion launch of this frame carries the normals role for the hinted NEXT frame (at most one of them passes the gate).
-     * Not in event-timed replays (gsdf_profile): there the fusion launch is the plain one, so that what bench.py quotes as
-     * k_fuse's duration is the fusion work alone. */
-    const bool pre = fuse_after && !c->profiling && c->nrm_ready_depth == depth_dev && c->nrm_ready_set >= 0 && iters > 0;
-    const int fuse_set = pre ? c->nrm_ready_set : 2;
-    const unsigned int ride_token = pre ? c->nrm_ready_token : 0u;
-    /* Both round-6 steps -- the next frame's normals in the fusion's tail, the fusion launch standing in for the first batch's last
-     * tracker launch -- pay where optimize() ends within the first batch and the fusion RUNS behind it.  Frames that converge late or
-     * never come in stretches (the reference's tracker cycles on them), and there the extra workgroups only look at a closed gate
-     * and the stand-in's head is followed by a head-less launch anyway (measured: -1 ... -2 % on the bench's default window): the
-     * host takes the old route while the last tracked frame whose end it KNOWS needed more than the first batch (a hint for the
-     * hint: the progress word of that frame's heads, read without waiting -- in such a stretch the host has just waited for it). */
-    if (fuse_after && c->progress && c->prev_track_serial) {
-        const unsigned int w = c->progress[0];
-        if ((w >> 16) == c->prev_track_serial && (w & 0x8000u)) c->prev_slow = (int)(w & 0x7FFFu) > c->prev_first_last;
-    }
-    /* ... and not while the fusion uses the larger LDS table (far geometry): that instantiation with the normals role is at the
-     * register limit and moves its records unpaired, with the head it spills -- both cost more than the step saves.  The choice is
-     * read ONCE here and handed to every fusion launch of this frame: the word it comes from is written by the device while the
-     * host runs, and a second read could pick the larger table for a launch that carries the normals role or the head. */
-    const int far = fuse_far_table(c);
-    const bool new_route = fuse_after && !c->profiling && iters > 0 && !c->prev_slow && !far;
-    const float* hint = new_route ? c->hint_next : nullptr;
-    c->nrm_ready_depth = nullptr;        /* consumed (or not ours) */
-    c->hint_next = nullptr;
-    if (hint == depth_dev) hint = nullptr;
-    int next_set = 0;
-    unsigned int next_token = 0u;
-    if (hint) {
-        next_set = fuse_set == 0 ? 1 : 0;                     /* whichever of sets 0 / 1 this frame's fusion does not read */
-        if (++c->nrm_token_ctr == 0u) c->nrm_token_ctr = 1u;
-        next_token = c->nrm_token_ctr;
-        c->nrm_ready_depth = hint; c->nrm_ready_set = next_set; c->nrm_ready_token = next_token;
-    }
+    track_route(f);
     if (iters <= 0) {
         gsdf_launch_track_none(c->stream, c->st);
-        return fuse_after ? enqueue_fuse(c, depth_dev, unused, 1, far, false) : GSDF_OK;
+        return fuse_after ? f.queue_fusion() : GSDF_OK;
     }
     if (iters > 0x7FFF) return fail(GSDF_ERR_INVALID, "num_iterations must be <= 32767");
-    gsdf_normals_job nj;
-    std::memset(&nj, 0, sizeof(nj));
-    if (fuse_after) {                    /* the frame's normals ride along with its first passes (unless computed ahead: ride_token) */
-        const size_t N = (size_t)c->W * c->H;
-        nj.nc = c->ncache();
-        nj.nx = c->normals + (size_t)(3 * fuse_set) * N; nj.ny = nj.nx + N; nj.nz = nj.nx + 2 * N;    /* set 2, or the hinted one */
-        nj.token = ride_token;
-        nj.deferred_count = c->deferred_count;
-        nj.stats = stats_of(c, nj.nx);
-        nj.r = c->win / 2; nj.ntx = 0;
-        nj.tile_first = 0; nj.tile_count = 0;
-    }
-    gsdf_track_params tp;
-    tp.max_passes = iters;
-    tp.conv_sq = conv * conv;                                /* RigidOptimizer.h:72 */
-    tp.damping = damping;
-    c->track_serial = (c->track_serial + 1u) & 0xFFFFu;
-    if (c->track_serial == 0) c->track_serial = 1;
-    tp.serial = c->track_serial;
-    const bool adaptive = c->adaptive && c->progress;
-    if (fuse_after) {                                        /* (the last launch index of this frame's first batch) */
-        c->prev_track_serial = tp.serial;
-        c->prev_first_last = std::min(iters, (adaptive ? c->first_batch : iters + 1) - 1);
-    }
-    tp.progress = adaptive ? c->progress_dev : nullptr;
-    tp.debug = c->debug >> 16;
-    tp.n_track_blocks = c->track_blocks;
-    tp.sampling = sampling;
-    tp.head_done = 0;
+    track_jobs(f, conv, damping, sampling);
     const int base = c->map_type == GSDF_MAP_BASE;
     /* (k_track_all has the grad gather only: a base context runs the per-pass launches) */
-    if (sampling == 1 && !base && c->persist && c->track_rows && c->track_blocks <= 2 * GSDF_TRACK_MAXBLK) {
-        /* the whole optimize() as one launch; the frame's fusion, gated on the device by done && converged, right behind it */
-        tp.pass_index = 0;
-        tp.rot = 0;
-        tp.progress = c->progress_dev;
-        {
-            prof_scope ps(c, 2);
-            gsdf_launch_track_all(c->stream, g, depth_dev, c->tab, c->st, c->track_rows, c->track_abort, c->track_blocks, tp,
-                                  fuse_after ? &nj : nullptr);
-        }
-        if (fuse_after) {
-            const int rc = enqueue_fuse(c, depth_dev, unused, 1, far, true, fuse_set, hint, nullptr, next_set, next_token);   /* main_scan_3d.cpp:261-265 */
-            if (rc) return rc;
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(GSDF_ERR_HIP, std::string("tracking launch: ") + hipGetErrorString(e));
-        return GSDF_OK;
-    }
-    int k = 0, batch_no = 0;
-    int batch = adaptive ? c->first_batch : iters + 1;
-    /* The frame's first fusion launch stands in for the LAST tracker launch of the first batch (k_fuse<.., HEAD>): that launch's
-     * head -- for the usual frame the closing one of optimize() -- runs in workgroup 0 of the fusion launch, which every other
-     * workgroup of it follows; a launch and a kernel boundary less per frame.  If optimize() has not ended with that head the
-     * next batch starts with a tracker launch of the same index that skips its head (head_done).  Not in event-timed replays:
-     * what bench.py quotes as k_fuse's duration is the fusion work alone. */
-    const bool fuse_head = new_route && adaptive && c->fuse_head;
-    bool headless = false;                                   /* the next launch's head was performed by a fusion launch */
-    while (k <= iters) {
-        const int last = std::min(iters, k + batch - 1);
-        const bool stand_in = fuse_head && batch_no == 0 && last >= 1;
-        for (; k <= last; ++k) {
-            if (stand_in && k == last) continue;             /* its head is the fusion launch's */
-            tp.pass_index = k;
-            tp.head_done = headless ? 1 : 0;
-            headless = false;
-            tp.rot = c->track_rot;
-            c->track_rot = (c->track_rot + 1u) % 3u;          /* kept in [0, 3): no discontinuity at wrap-around */
-            /* The frame's normals tiles ride in its first launches: nrm_split per cent in launch 0, nrm_split2 in launch 1, the rest
-             * in launch 2.  Launch 1 always exists (it is at least the head of pass 0), launch 2 when the first batch has three
-             * launches and optimize() may take two passes.  Next to the one tracker workgroup per CU a launch hides a share of the
-             * tiles; launch 0 has no head and ends early, so it takes the smallest one.  Tile 0 (it resets the frame's deferred list)
-             * stays in launch 0. */
-            const gsdf_normals_job* job = nullptr;
-            if (fuse_after && k <= 2) {
-                const int tiles = gsdf_normals_tiles(c->W, c->H);
-                /* tracker launches of the first batch (the fusion launch may stand in for its last one: no riders there) */
-                const int nl = batch_no == 0 ? (stand_in ? last : last + 1) : 3;
-                const bool three = iters >= 2 && batch >= 3 && nl >= 3;
-                const int b1 = nl >= 2 ? std::max(1, tiles * c->nrm_split / 100) : tiles;
-                const int b2 = three ? std::min(tiles, std::max(b1, tiles * (c->nrm_split + c->nrm_split2) / 100)) : tiles;
-                const int lo = k == 0 ? 0 : k == 1 ? b1 : b2, hi = k == 0 ? b1 : k == 1 ? b2 : tiles;
-                if (hi > lo && (k < 2 || three)) { nj.tile_first = lo; nj.tile_count = hi - lo; job = &nj; }
-            }
-            prof_scope ps(c, 2);
-            gsdf_launch_track_pass(c->stream, g, depth_dev, c->tab, c->st, c->partials, c->track_blocks, tp, job, base);
-        }
-        /* The fusion is queued behind the FIRST batch unseen (the usual frame ends there and must not wait for the host) and
-         * behind the last one (nothing follows it).  Behind the batches in between it would nearly always be a gated launch
-         * that finds optimize() still running -- 3 us each, 3 per frame that never converges -- so there it is queued only
-         * once the progress word says that optimize() has ended (the frame that converges late pays the host's look). */
-        bool fuse_queued = false;
-        if (fuse_after && (batch_no == 0 || last == iters || !c->lazy_fuse)) {
-            gsdf_fuse_head hd;
-            std::memset(&hd, 0, sizeof(hd));
-            if (stand_in) {
-                hd.k = last;
-                hd.rot_prev = (c->track_rot + 2u) % 3u;      /* the buffer the last launch issued (pass last - 1) accumulated into */
-                hd.conv_sq = tp.conv_sq; hd.damping = tp.damping; hd.max_passes = tp.max_passes;
-                hd.serial = tp.serial; hd.progress = tp.progress; hd.rows = c->partials; hd.debug = tp.debug;
-            }
-            const int rc = enqueue_fuse(c, depth_dev, unused, 1, far, true, fuse_set, hint, stand_in ? &hd : nullptr, next_set, next_token);   /* main_scan_3d.cpp:261-265 */
-            if (rc) return rc;
-            fuse_queued = true;
-        }
-        ++batch_no;
-        if (last == iters) break;                            /* the head-only launch always ends optimize() */
-        int ended = follow_progress(c, tp.serial, last);
-        if (ended < 0) {                                     /* the device is far behind: wait for it properly */
-            gsdf_dev_state s;
-            if (hipMemcpyAsync(&s, c->st, sizeof(s), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                hipStreamSynchronize(c->stream) != hipSuccess)
-                return fail(GSDF_ERR_HIP, "tracking: device state read failed");
-            ended = s.done;
-        }
-        if (ended) {
-            if (fuse_after && !fuse_queued) {
-                const int rc = enqueue_fuse(c, depth_dev, unused, 1, far, true, fuse_set, hint, nullptr, next_set, next_token);
-                if (rc) return rc;
-            }
-            break;
-        }
-        if (stand_in) { k = last; headless = true; }         /* launch `last` comes now, without the head the fusion launch performed */
-        batch = c->next_batch;
-    }
+    if (sampling == 1 && !base && c->persist && c->track_rows && c->track_blocks <= 2 * GSDF_TRACK_MAXBLK) return track_one_launch(f);
+    const int rc = track_batched(f, base);
+    if (rc) return rc;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(GSDF_ERR_HIP, std::string("tracking launch: ") + hipGetErrorString(e));
     return GSDF_OK;
@@ -466,30 +513,22 @@ int read_state(gsdf_ctx* c, gsdf_dev_state* out) {
 
 /* launches the GT-pose fusion that waits for its successor (gsdf_update_dev), if any */
 int gsdf_flush_pending(gsdf_ctx* c) {
-    if (!c || !c->pending.valid) return GSDF_OK;
-    c->pending.valid = false;
+    if (!c || !c->ahead.pending.valid) return GSDF_OK;
+    c->ahead.release();
     if (hipSetDevice(c->device) != hipSuccess) return fail(GSDF_ERR_HIP, "hipSetDevice");
     const size_t N = (size_t)c->W * c->H;
-    return launch_fuse(c, c->pending.depth, c->normals + (size_t)c->pending.set * 3 * N, c->pending.pose, 0, fuse_far_table(c), nullptr, nullptr);
+    const gsdf_lookahead::pending_fuse& p = c->ahead.pending;
+    return launch_fuse(c, p.depth, c->normals + (size_t)p.set * 3 * N, p.pose, 0, fuse_far_table(c), nullptr, nullptr);
 }
-#define GSDF_FLUSH(c) do { if ((c) && (c)->pending.valid) { const int rc_ = gsdf_flush_pending(c); if (rc_) return rc_; } } while (0)
+#define GSDF_FLUSH(c) do { if ((c) && (c)->ahead.pending.valid) { const int rc_ = gsdf_flush_pending(c); if (rc_) return rc_; } } while (0)
 /* The staging entries (gsdf_dev_upload*) write device memory the caller names.  A GT-pose fusion that still waits for its
  * successor reads its depth image when it is LAUNCHED, so a copy into that image has to come behind the launch: the pattern
  * upload(buf) -> update_dev(buf) -> upload(buf) -> update_dev(buf) on ONE staging buffer is correct by stream order only if
  * the waiting fusion is launched before the second copy is queued.  Copies elsewhere leave the pipelining alone. */
 static int flush_if_overlaps(gsdf_ctx* c, const void* dst, int64_t bytes) {
-    if (c && (c->nrm_ready_depth || c->hint_next)) {
-        /* a copy into a frame whose normals were computed ahead (gsdf_hint_next_depth_dev), or that is hinted: those belong to the
-         * old contents -- forget them, the frame's own tracker launches compute its normals then */
-        const uintptr_t a0 = (uintptr_t)dst, a1 = a0 + (uintptr_t)std::max<int64_t>(bytes, 0);
-        const size_t fb = (size_t)c->W * c->H * sizeof(float);
-        for (const float** q : { &c->nrm_ready_depth, &c->hint_next })
-            if (*q) { const uintptr_t b0 = (uintptr_t)*q; if (a0 < b0 + fb && b0 < a1) *q = nullptr; }
-    }
-    if (!c || !c->pending.valid) return GSDF_OK;
-    const uintptr_t a0 = (uintptr_t)dst, a1 = a0 + (uintptr_t)std::max<int64_t>(bytes, 0);
-    const uintptr_t b0 = (uintptr_t)c->pending.depth, b1 = b0 + (size_t)c->W * c->H * sizeof(float);
-    if (a0 < b1 && b0 < a1) return gsdf_flush_pending(c);
+    /* (a copy into a frame whose normals were computed ahead (gsdf_hint_next_depth_dev), or that is hinted: those belong to the
+     * old contents -- forgotten, the frame's own tracker launches compute its normals then) */
+    if (c && c->ahead.range_changes(dst, (size_t)std::max<int64_t>(bytes, 0), c->frame_bytes())) return gsdf_flush_pending(c);
     return GSDF_OK;
 }
 
@@ -562,6 +601,10 @@ int gsdf_debug_read(gsdf_ctx* c, unsigned long long out[24]) {
     if (hipMemcpy(&h, c->st, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return GSDF_ERR_HIP;
     for (int i = 0; i < 24; ++i) out[i] = h.dbg[i];
     return GSDF_OK;
+}
+/* normals_tile_split as enqueue_track uses it, for the tests: no context, no device.  1 = launch k computes the tiles [*lo, *hi) */
+int gsdf_debug_normals_tile_split(int tiles, int k, int launches, int iters, int batch, int nrm_split, int nrm_split2, int* lo, int* hi) {
+    return lo && hi && normals_tile_split(tiles, k, launches, iters, batch, nrm_split, nrm_split2, lo, hi) ? 1 : 0;
 }
 const char* gsdf_version(void) { return "gsdf-mi355x 0.2 (gfx950) +experiments"; }
 #else
@@ -700,10 +743,8 @@ void gsdf_destroy(gsdf_ctx* c) {
 int gsdf_reset(gsdf_ctx* c) {
     if (!c) return fail(GSDF_ERR_INVALID, "null context");
     HIP_TRY(hipSetDevice(c->device));
-    c->pending.valid = false;                              /* a fusion that was never launched is dropped with the map */
+    c->ahead.forget_all();                                 /* a fusion that was never launched is dropped with the map; gsdf_hint_next_depth_dev: a new scan starts without them */
     c->fuse_launches = 0; c->far_table_launches = 0;
-    c->hint_next = nullptr; c->nrm_ready_depth = nullptr;  /* (gsdf_hint_next_depth_dev: a new scan starts without them) */
-    c->prev_track_serial = 0; c->prev_slow = false;
     if (c->deferred_count) HIP_TRY(hipMemsetAsync(c->deferred_count, 0, sizeof(unsigned int), c->stream));
     gsdf_launch_table_clear(c->stream, c->tab, c->n_slots);
     if (c->vis) HIP_TRY(hipMemsetAsync(c->vis, 0, c->n_slots * (size_t)c->vis_words * sizeof(uint32_t), c->stream));
@@ -773,7 +814,7 @@ int gsdf_set_zrange(gsdf_ctx* c, float zmin, float zmax) {
     if (zmin != c->zmin || zmax != c->zmax) {
         /* the tile statistics of normals computed ahead (gsdf_hint_next_depth_dev) were taken under the old range: a tile with no
          * pixel inside it would count no valid pixel and never be walked.  Forget them; the next frame computes its own. */
-        c->hint_next = nullptr; c->nrm_ready_depth = nullptr;
+        c->ahead.forget_frames();
     }
     c->zmin = zmin; c->zmax = zmax;
     return GSDF_OK;
@@ -792,7 +833,7 @@ int gsdf_normals_init(gsdf_ctx* c, int W, int H, const float K[9], int win) {
     c->track_rows = nullptr; c->track_abort = nullptr;
     c->tile_flags = nullptr; c->tile_order = nullptr; c->tile_stats = nullptr;
     c->planes = c->depth_stage = c->normals = nullptr; c->partials = nullptr; c->depth_sampled = nullptr;
-    c->hint_next = nullptr; c->nrm_ready_depth = nullptr;
+    c->ahead.forget_frames();
     c->blk_counters = nullptr; c->frame_log = nullptr; c->deferred = nullptr; c->deferred_count = nullptr; c->fuse_ticket = nullptr;
     c->W = W; c->H = H; c->win = win;
     std::memcpy(c->K, K, 9 * sizeof(float));
@@ -899,20 +940,18 @@ int gsdf_update_dev(gsdf_ctx* c, const float* depth_dev, const float R[9], const
      * fusion first (gsdf_flush_pending at the top of every other entry), so the deferral is invisible except in time.
      * The two sets of normal planes alternate. */
     const size_t N = (size_t)c->W * c->H;
-    const int set = c->nrm_parity;
-    c->nrm_parity ^= 1;
-    c->nrm_ready_depth = nullptr;                          /* sets 0 / 1 are this path's: a hinted tracked frame's normals are gone */
+    const int set = c->ahead.take_gt_set();                /* sets 0 / 1 are this path's: a hinted tracked frame's normals are gone */
     float* nrm = c->normals + (size_t)set * 3 * N;
-    if (!c->pending.valid) {
+    if (!c->ahead.pending.valid) {
         gsdf_launch_normals(c->stream, c->geom(), c->win, c->ncache(), depth_dev, nrm, nrm + N, nrm + 2 * N, nullptr, nullptr, stats_of(c, nrm));
         HIP_TRY(hipGetLastError());
     } else {
-        const float* pn = c->normals + (size_t)c->pending.set * 3 * N;
-        int rc = launch_fuse(c, c->pending.depth, pn, c->pending.pose, 0, fuse_far_table(c), depth_dev, nrm);
-        c->pending.valid = false;
+        const gsdf_lookahead::pending_fuse& p = c->ahead.pending;
+        int rc = launch_fuse(c, p.depth, c->normals + (size_t)p.set * 3 * N, p.pose, 0, fuse_far_table(c), depth_dev, nrm);
+        c->ahead.release();
         if (rc) return rc;
     }
-    c->pending.valid = true; c->pending.depth = depth_dev; c->pending.pose = pose; c->pending.set = set;
+    c->ahead.hold(depth_dev, pose, set);
     return GSDF_OK;
 }
 
@@ -980,14 +1019,14 @@ int gsdf_track_sampled(gsdf_ctx* c, const float* depth_host, const float K[9], f
 
 int gsdf_hint_next_depth_dev(gsdf_ctx* c, const float* next_depth_dev) {
     if (!c) return fail(GSDF_ERR_INVALID, "null context");
-    c->hint_next = next_depth_dev;                       /* nullptr withdraws it; no device work, no flush */
+    c->ahead.hint(next_depth_dev);                       /* nullptr withdraws it; no device work, no flush */
     return GSDF_OK;
 }
 
 int gsdf_track_and_fuse_ahead_dev(gsdf_ctx* c, const float* depth_dev, const float* next_depth_dev, const float K[9],
                                   int num_iterations, float conv_threshold, float damping) {
     if (!c) return fail(GSDF_ERR_INVALID, "null context");
-    c->hint_next = next_depth_dev;
+    c->ahead.hint(next_depth_dev);
     return gsdf_track_and_fuse_dev(c, depth_dev, K, num_iterations, conv_threshold, damping);
 }
 
@@ -1698,9 +1737,7 @@ int gsdf_dev_free(gsdf_ctx* c, void* dev_ptr) {
             (void)hipGetLastError();
             base = dev_ptr; bytes = 1;
         }
-        const uintptr_t a0 = (uintptr_t)base, a1 = a0 + bytes;
-        for (const float** q : { &c->nrm_ready_depth, &c->hint_next })
-            if (*q && (uintptr_t)*q >= a0 && (uintptr_t)*q < a1) *q = nullptr;
+        (void)c->ahead.range_changes(base, bytes, c->frame_bytes());   /* (a waiting fusion was launched above) */
     }
     HIP_TRY(hipFree(dev_ptr));
     return GSDF_OK;
@@ -1787,17 +1824,9 @@ int gsdf_dev_upload_ahead(gsdf_ctx* c, void* dev_dst, const void* host_src, int6
     HIP_TRY(hipSetDevice(c->device));
     /* (a caller that keeps to the contract -- dev_dst is out of the stream's reach: its last reader passed a gsdf_mark, which
      * launched any waiting fusion -- never gets here with an overlap; the copy stream is not ordered behind the kernels) */
-    if (c->pending.valid) {
-        const uintptr_t a0 = (uintptr_t)dev_dst, b0 = (uintptr_t)c->pending.depth;
-        if (a0 < b0 + (size_t)c->W * c->H * sizeof(float) && b0 < a0 + (uintptr_t)bytes)
-            return fail(GSDF_ERR_INVALID, "gsdf_dev_upload_ahead into the depth image of a fusion that has not run yet (record a gsdf_mark "
-                                          "behind its gsdf_update_dev and wait for it first)");
-    }
-    for (const float** q : { &c->nrm_ready_depth, &c->hint_next })      /* new contents: normals computed ahead are the old frame's */
-        if (*q) {
-            const uintptr_t a0 = (uintptr_t)dev_dst, b0 = (uintptr_t)*q;
-            if (a0 < b0 + (size_t)c->W * c->H * sizeof(float) && b0 < a0 + (uintptr_t)bytes) *q = nullptr;
-        }
+    if (c->ahead.range_changes(dev_dst, (size_t)bytes, c->frame_bytes()))   /* new contents: normals computed ahead are the old frame's */
+        return fail(GSDF_ERR_INVALID, "gsdf_dev_upload_ahead into the depth image of a fusion that has not run yet (record a gsdf_mark "
+                                      "behind its gsdf_update_dev and wait for it first)");
     if (!c->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     HIP_TRY(hipMemcpyAsync(dev_dst, host_src, (size_t)bytes, hipMemcpyHostToDevice, c->copy_stream));
     hipEvent_t e = nullptr;                                      /* (a pool of their own: these keep the default fences) */

@@ -9,6 +9,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <deque>
 #include <string>
 #include <utility>
@@ -40,14 +41,90 @@ inline int gsdf_fail(int code, const std::string& msg) {
             return gsdf_fail(GSDF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
     } while (0)
 
+/* the pinned progress word the pass heads write: serial << 16 | done << 15 | passes (gsdf_track_params::progress) */
+struct gsdf_progress { unsigned int serial; bool done; int passes; };
+inline gsdf_progress gsdf_progress_decode(unsigned int w) { return { w >> 16, (w & 0x8000u) != 0u, (int)(w & 0x7FFFu) }; }
+
+/* how a tracked frame uses what was computed ahead of it, and what it promises to the next one (gsdf_lookahead::consume) */
+struct gsdf_frame_route {
+    int fuse_set = 2;                              /* the normal planes the frame's fusion reads: set 2, or the hinted one */
+    unsigned int ride_token = 0;                   /* != 0: the frame's normals were computed ahead under this token */
+    const float* hint = nullptr;                   /* the NEXT frame, whose normals every fusion launch of this frame carries ... */
+    int next_set = 0;                              /* ... into this set ... */
+    unsigned int next_token = 0;                   /* ... leaving this token in st->nrm_token if its gate was open */
+};
+
+/* The frame loop's look-ahead state: everything computed or promised AHEAD of the frame an entry works on.  The operations
+ * below are the only code that writes it (reading through gsdf_ctx::ahead is fine): an entry that invalidates a buffer or a
+ * statistic names what happens, not the fields to null. */
+struct gsdf_lookahead {
+    /* a GT-pose fusion whose launch waits for the next gsdf_update_dev (its launch then also computes that frame's normals) */
+    struct pending_fuse { bool valid = false; const float* depth = nullptr; gsdf_pose_arg pose; int set = 0; } pending;
+    int nrm_parity = 0;                            /* which set of normal planes the next GT-pose fusion uses (0 / 1; set 2: tracked frames) */
+    /* gsdf_hint_next_depth_dev: the frame the NEXT gsdf_track_and_fuse_dev will be called with (set by the caller, consumed by the
+     * next frame entry), and the frame whose normals a fusion launch has already computed into set nrm_ready_set (0 / 1) */
+    const float* hint_next = nullptr;
+    const float* nrm_ready_depth = nullptr;
+    int nrm_ready_set = -1;
+    unsigned int nrm_ready_token = 0, nrm_token_ctr = 0;   /* what that fusion launch leaves in st->nrm_token when its gate was open */
+    unsigned int prev_track_serial = 0; int prev_first_last = 0; bool prev_slow = false;   /* the last tracked frame: did it need more than its first batch (as far as the host knows)? */
+
+    /* does [p, p + bytes) overlap the frame (frame_bytes long) at `frame`? */
+    static bool overlaps(const void* p, size_t bytes, const float* frame, size_t frame_bytes) {
+        const uintptr_t a0 = (uintptr_t)p, b0 = (uintptr_t)frame;
+        return a0 < b0 + frame_bytes && b0 < a0 + bytes;
+    }
+    void hint(const float* next_depth) { hint_next = next_depth; }      /* nullptr withdraws it */
+    /* the frames named or computed ahead are forgotten: the next frame's own tracker launches compute its normals */
+    void forget_frames() { hint_next = nullptr; nrm_ready_depth = nullptr; }
+    /* ... and a fusion that was never launched is dropped, the last tracked frame forgotten (a new scan) */
+    void forget_all() { forget_frames(); pending.valid = false; prev_track_serial = 0; prev_slow = false; }
+    /* [p, p + bytes) is about to change or go away: a hinted frame or one whose normals were computed ahead in it belongs to the
+     * old contents -- forgotten.  Returns whether the waiting GT-pose fusion reads from it (the caller's to deal with). */
+    bool range_changes(const void* p, size_t bytes, size_t frame_bytes) {
+        for (const float** q : { &nrm_ready_depth, &hint_next })
+            if (*q && overlaps(p, bytes, *q, frame_bytes)) *q = nullptr;
+        return pending.valid && overlaps(p, bytes, pending.depth, frame_bytes);
+    }
+    /* the set of the next GT-pose fusion; sets 0 / 1 are also where a hinted tracked frame's normals wait: those are gone */
+    int take_gt_set() { const int set = nrm_parity; nrm_parity ^= 1; nrm_ready_depth = nullptr; return set; }
+    void hold(const float* depth, const gsdf_pose_arg& pose, int set) { pending.valid = true; pending.depth = depth; pending.pose = pose; pending.set = set; }
+    void release() { pending.valid = false; }
+    /* the tracked frame `serial` was queued; first_last: the last launch index of its first batch */
+    void tracked(unsigned int serial, int first_last) { prev_track_serial = serial; prev_first_last = first_last; }
+    /* a look at the progress word without waiting: if it tells how the last tracked frame ended, was that beyond its first batch? */
+    void note_progress(unsigned int word) {
+        const gsdf_progress p = gsdf_progress_decode(word);
+        if (prev_track_serial && p.serial == prev_track_serial && p.done) prev_slow = p.passes > prev_first_last;
+    }
+    /* gsdf_hint_next_depth_dev, for the tracked frame at depth_dev: (1) its normals may already lie in set 0 / 1 -- the previous
+     * frame's fusion computed them in its tail IF IT RAN (a fusion whose gate stays closed does not: its tail is not idle, the
+     * tiles would run in the open); the frame's riders are queued as ever and leave at once when they find the frame's token in
+     * st->nrm_token; (2) if the new route is taken every fusion launch of this frame carries the normals role for the hinted
+     * NEXT frame (at most one of them passes the gate).  `ahead_ok`: false in event-timed replays (gsdf_profile) -- there the
+     * fusion launch is the plain one, so that what bench.py quotes as k_fuse's duration is the fusion work alone -- and for
+     * frames that are not tracked and fused. */
+    gsdf_frame_route consume(const float* depth_dev, bool ahead_ok, bool new_route) {
+        gsdf_frame_route r;
+        if (ahead_ok && nrm_ready_depth == depth_dev && nrm_ready_set >= 0) { r.fuse_set = nrm_ready_set; r.ride_token = nrm_ready_token; }
+        r.hint = new_route && hint_next != depth_dev ? hint_next : nullptr;
+        forget_frames();                             /* consumed (or not ours) */
+        if (r.hint) {
+            r.next_set = r.fuse_set == 0 ? 1 : 0;    /* whichever of sets 0 / 1 this frame's fusion does not read */
+            if (++nrm_token_ctr == 0u) nrm_token_ctr = 1u;
+            r.next_token = nrm_token_ctr;
+            nrm_ready_depth = r.hint; nrm_ready_set = r.next_set; nrm_ready_token = r.next_token;
+        }
+        return r;
+    }
+};
+
 struct gsdf_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    /* a GT-pose fusion whose launch waits for the next gsdf_update_dev (its launch then also computes that frame's normals) */
-    struct pending_fuse { bool valid = false; const float* depth = nullptr; gsdf_pose_arg pose; int set = 0; } pending;
+    gsdf_lookahead ahead;                          /* the frame loop's look-ahead state (above) */
     int defer = 1;                                 /* pipeline runs of gsdf_update_dev that way (GSDF_DEFER=0: launch at once) */
     int nrm_split = 30, nrm_split2 = 40;           /* per cent of a tracked frame's normals tiles computed in its first / second tracker launch (rest: third) */
-    int nrm_parity = 0;                            /* which set of normal planes the next GT-pose fusion uses (0 / 1; set 2: tracked frames) */
     /* MapGradPixelSdf / Sdf members */
     float voxel_size = 0, voxel_size_inv = 0, T = 0, inv_T = 0;
     float zmin = 0.5f, zmax = 3.5f;                /* Sdf.h:67-68 */
@@ -86,14 +163,7 @@ struct gsdf_ctx {
     unsigned long long* rc_counts = nullptr;       /* raycaster: per-workgroup rows of (samples, records, fast / slow iterations of wave 0) */
     size_t rc_rows = 0;
     long long rc_iters[2] = { 0, 0 };              /* loop iterations of the workgroups' wave 0 as of the last gsdf_raycast_counters */
-    /* gsdf_hint_next_depth_dev: the frame the NEXT gsdf_track_and_fuse_dev will be called with (set by the caller, consumed by the
-     * next frame entry), and the frame whose normals a fusion launch has already computed into set nrm_ready_set (0 / 1) */
     bool fuse_head = true;                         /* the frame's first fusion launch performs the head of the first batch's last tracker launch (GSDF_FUSE_HEAD) */
-    const float* hint_next = nullptr;
-    const float* nrm_ready_depth = nullptr;
-    int nrm_ready_set = -1;
-    unsigned int prev_track_serial = 0; int prev_first_last = 0; bool prev_slow = false;   /* the last tracked frame: did it need more than its first batch (as far as the host knows)? */
-    unsigned int nrm_ready_token = 0, nrm_token_ctr = 0;   /* what that fusion launch leaves in st->nrm_token when its gate was open */
     float* depth_sampled = nullptr;                /* the compacted pixels of gsdf_track_sampled (sampling > 1), lazily allocated */
     void* scratch = nullptr;                       /* device scratch of gsdf_query / gsdf_get_voxels for small batches (GSDF_SCRATCH_BYTES) */
     bool occ_dirty = false;                        /* blocks may have been inserted since the raycaster's filters (gsdf_table::occ) were built */
@@ -164,6 +234,7 @@ struct gsdf_ctx {
     std::vector<float> prof_each[GSDF_PROF_SLOTS];  /* every launch's duration since the last gsdf_profile(c, 1) (gsdf_profile_read_launches) */
     long long prof_n[GSDF_PROF_SLOTS] = { 0 };
 
+    size_t frame_bytes() const { return (size_t)W * H * sizeof(float); }
     gsdf_frame_geom geom() const {
         gsdf_frame_geom g;
         g.W = W; g.H = H;

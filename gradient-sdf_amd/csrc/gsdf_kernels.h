@@ -107,28 +107,35 @@ struct gsdf_fuse_head {
     const double* rows;           /* the partial-sum buffers (3 x GSDF_TRACK_ROWSET) */
     int debug;
 };
-/* use_dev_pose: take R,t from st->R / st->pose7 and skip the launch unless st->converged */
-void gsdf_launch_fuse(hipStream_t s, const gsdf_frame_geom& g, const gsdf_ncache& nc, const float* depth,
-                      const float* nx, const float* ny, const float* nz, const gsdf_pose_arg& pose,
-                      int use_dev_pose, gsdf_table tab, gsdf_dev_state* st,
-                      unsigned long long* blk_counters /* [gsdf_fuse_grid_blocks][4] */,
-                      gsdf_deferred* deferred, unsigned int* deferred_count, unsigned int deferred_cap,
-                      unsigned int tag /* serial of the fusion launch, never 0 */,
-                      unsigned int* tile_flags /* [gsdf_fuse_grid_blocks] hand-off flags, zeroed once */,
-                      const uint32_t* tile_order /* [gsdf_fuse_grid_blocks] from gsdf_fuse_tile_order, on the device */,
-                      float* log_rows /* nullable: frame log, written when use_dev_pose */, long long max_rows,
-                      uint32_t* vis /* nullable: per-voxel frame bit-vectors */, int vis_words,
-                      int debug /* path-forcing / measurement switches, honoured by -DGSDF_EXPERIMENTS builds only */,
-                      unsigned int* ticket /* two device words, zeroed once: arrivals of finished workgroups of k_fuse / of k_fuse_resolve */,
-                      int resolve_follows /* also queue k_fuse_resolve (long deferred lists) */,
-                      unsigned int* host_note /* nullable, 2 pinned host words: length of the deferred list, tiles too big for the small LDS table */,
-                      int far_table /* use the kernel with the larger LDS table */,
-                      const gsdf_fuse_head* head /* nullable: also perform the closing head of optimize() (use_dev_pose only) */,
-                      const float* next_depth /* nullable: the launch also computes the normals of this (the next) frame ... */,
-                      float* next_nx, float* next_ny, float* next_nz /* ... into these planes */, int win,
-                      const uint32_t* tile_stats /* this frame's tile statistics (written with its normals) */,
-                      uint32_t* next_tile_stats /* the next frame's, written by the launch's normals workgroups */,
-                      unsigned int next_token /* tracked frames: left in st->nrm_token by the normals role when it ran */);
+/* One k_fuse launch: depth + its normal planes -> the map */
+struct gsdf_fuse_launch {
+    gsdf_frame_geom g;
+    gsdf_ncache nc;
+    const float *depth, *nx, *ny, *nz;
+    gsdf_pose_arg pose;
+    int use_dev_pose;             /* take R,t from st->R / st->pose7 and skip the launch unless st->converged */
+    gsdf_table tab;
+    gsdf_dev_state* st;
+    unsigned long long* blk_counters;   /* [gsdf_fuse_grid_blocks][4] */
+    gsdf_deferred* deferred; unsigned int* deferred_count; unsigned int deferred_cap;
+    unsigned int tag;             /* serial of the fusion launch, never 0 */
+    unsigned int* tile_flags;     /* [gsdf_fuse_grid_blocks] hand-off flags, zeroed once */
+    const uint32_t* tile_order;   /* [gsdf_fuse_grid_blocks] from gsdf_fuse_tile_order, on the device */
+    float* log_rows; long long max_rows;   /* nullable: frame log, written when use_dev_pose */
+    uint32_t* vis; int vis_words; /* nullable: per-voxel frame bit-vectors */
+    int debug;                    /* path-forcing / measurement switches, honoured by -DGSDF_EXPERIMENTS builds only */
+    unsigned int* ticket;         /* two device words, zeroed once: arrivals of finished workgroups of k_fuse / of k_fuse_resolve */
+    int resolve_follows;          /* also queue k_fuse_resolve (long deferred lists) */
+    unsigned int* host_note;      /* nullable, 2 pinned host words: length of the deferred list, tiles too big for the small LDS table */
+    int far_table;                /* use the kernel with the larger LDS table */
+    const gsdf_fuse_head* head;   /* nullable: also perform the closing head of optimize() (use_dev_pose only) */
+    const float* next_depth;      /* nullable: the launch also computes the normals of this (the next) frame ... */
+    float *next_nx, *next_ny, *next_nz; int win;   /* ... into these planes */
+    const uint32_t* tile_stats;   /* this frame's tile statistics (written with its normals) */
+    uint32_t* next_tile_stats;    /* the next frame's, written by the launch's normals workgroups */
+    unsigned int next_token;      /* tracked frames: left in st->nrm_token by the normals role when it ran */
+};
+void gsdf_launch_fuse(hipStream_t s, const gsdf_fuse_launch& f);
 int  gsdf_fuse_grid_blocks(int W, int H);
 void gsdf_fuse_tile_order(int W, int H, uint32_t* order_host /* [gsdf_fuse_grid_blocks] */);
 /* per-launch parameters of one Gauss-Newton pass (RigidOptimizer.h:57-62) */

@@ -1565,52 +1565,44 @@ __global__ __launch_bounds__(256) void k_fuse_resolve(const gsdf_deferred* list,
     }
 }
 
-void gsdf_launch_fuse(hipStream_t s, const gsdf_frame_geom& g, const gsdf_ncache& nc, const float* depth,
-                      const float* nx, const float* ny, const float* nz, const gsdf_pose_arg& pose,
-                      int use_dev_pose, gsdf_table tab, gsdf_dev_state* st, unsigned long long* blk_counters,
-                      gsdf_deferred* deferred, unsigned int* deferred_count, unsigned int deferred_cap,
-                      unsigned int tag, unsigned int* tile_flags, const uint32_t* tile_order, float* log_rows,
-                      long long max_rows, uint32_t* vis, int vis_words, int debug, unsigned int* ticket, int resolve_follows,
-                      unsigned int* host_note, int far_table, const gsdf_fuse_head* head, const float* next_depth, float* next_nx,
-                      float* next_ny, float* next_nz, int win, const uint32_t* tile_stats, uint32_t* next_tile_stats,
-                      unsigned int next_token) {
+void gsdf_launch_fuse(hipStream_t s, const gsdf_fuse_launch& f) {
     fuse_args a;
-    a.tile_stats = tile_stats; a.nrm_stats = next_tile_stats;
-    a.host_note = host_note;
-    a.ticket = ticket; a.log_rows = use_dev_pose ? log_rows : nullptr; a.max_rows = max_rows; a.resolve_follows = resolve_follows;
-    a.vis = vis; a.vis_words = vis_words;
-    a.debug = debug;
-    a.g = g; a.nc = nc; a.depth = depth; a.nx = nx; a.ny = ny; a.nz = nz; a.pose = pose;
-    a.use_dev_pose = use_dev_pose; a.tab = tab; a.st = st; a.blk_counters = blk_counters;
-    a.deferred = deferred; a.deferred_count = deferred_count; a.deferred_cap = deferred_cap; a.tag = tag;
-    const int ntx = (g.W + FUSE_T - 1) / FUSE_T, nty = (g.H + FUSE_TH - 1) / FUSE_TH;
-    gsdf_dev_state* gate = use_dev_pose ? st : nullptr;
-    a.tile_flags = tile_flags; a.ntx = ntx; a.nty = nty; a.tile_order = tile_order;
+    a.tile_stats = f.tile_stats; a.nrm_stats = f.next_tile_stats;
+    a.host_note = f.host_note;
+    a.ticket = f.ticket; a.log_rows = f.use_dev_pose ? f.log_rows : nullptr; a.max_rows = f.max_rows; a.resolve_follows = f.resolve_follows;
+    a.vis = f.vis; a.vis_words = f.vis_words;
+    a.debug = f.debug;
+    a.g = f.g; a.nc = f.nc; a.depth = f.depth; a.nx = f.nx; a.ny = f.ny; a.nz = f.nz; a.pose = f.pose;
+    a.use_dev_pose = f.use_dev_pose; a.tab = f.tab; a.st = f.st; a.blk_counters = f.blk_counters;
+    a.deferred = f.deferred; a.deferred_count = f.deferred_count; a.deferred_cap = f.deferred_cap; a.tag = f.tag;
+    const int ntx = (f.g.W + FUSE_T - 1) / FUSE_T, nty = (f.g.H + FUSE_TH - 1) / FUSE_TH;
+    gsdf_dev_state* gate = f.use_dev_pose ? f.st : nullptr;
+    a.tile_flags = f.tile_flags; a.ntx = ntx; a.nty = nty; a.tile_order = f.tile_order;
     const int n = ntx * nty;
     a.n_tiles = n;
-    a.nrm_depth = next_depth; a.nrm_x = next_nx; a.nrm_y = next_ny; a.nrm_z = next_nz;
-    a.nrm_r = win / 2; a.nrm_ntx = (g.W + NRM_TX - 1) / NRM_TX;
-    int extra = next_depth ? a.nrm_ntx * ((g.H + NRM_TY - 1) / NRM_TY) : 0;
+    a.nrm_depth = f.next_depth; a.nrm_x = f.next_nx; a.nrm_y = f.next_ny; a.nrm_z = f.next_nz;
+    a.nrm_r = f.win / 2; a.nrm_ntx = (f.g.W + NRM_TX - 1) / NRM_TX;
+    int extra = f.next_depth ? a.nrm_ntx * ((f.g.H + NRM_TY - 1) / NRM_TY) : 0;
     if (extra && !FUSE_CARRIES_NORMALS) {
-        gsdf_launch_normals(s, g, win, nc, next_depth, next_nx, next_ny, next_nz, nullptr, nullptr, next_tile_stats);
+        gsdf_launch_normals(s, f.g, f.win, f.nc, f.next_depth, f.next_nx, f.next_ny, f.next_nz, nullptr, nullptr, f.next_tile_stats);
         extra = 0;
     }
     std::memset(&a.hd, 0, sizeof(a.hd));
-    a.nrm_token = next_token;
-    if (head && use_dev_pose && head->k > 0) {
-        a.hd = *head;
+    a.nrm_token = f.next_token;
+    if (f.head && f.use_dev_pose && f.head->k > 0) {
+        a.hd = *f.head;
         if (extra) {
-            if (far_table) hipLaunchKernelGGL((k_fuse<FUSE_LCAP_FAR, true, true>), dim3(n + extra), dim3(FUSE_THREADS), 0, s, a);
+            if (f.far_table) hipLaunchKernelGGL((k_fuse<FUSE_LCAP_FAR, true, true>), dim3(n + extra), dim3(FUSE_THREADS), 0, s, a);
             else hipLaunchKernelGGL((k_fuse<FUSE_LCAP_NEAR, true, true>), dim3(n + extra), dim3(FUSE_THREADS), 0, s, a);
-        } else if (far_table) hipLaunchKernelGGL((k_fuse<FUSE_LCAP_FAR, false, true>), dim3(n), dim3(FUSE_THREADS), 0, s, a);
+        } else if (f.far_table) hipLaunchKernelGGL((k_fuse<FUSE_LCAP_FAR, false, true>), dim3(n), dim3(FUSE_THREADS), 0, s, a);
         else hipLaunchKernelGGL((k_fuse<FUSE_LCAP_NEAR, false, true>), dim3(n), dim3(FUSE_THREADS), 0, s, a);
     } else if (extra) {
-        if (far_table) hipLaunchKernelGGL((k_fuse<FUSE_LCAP_FAR, true, false>), dim3(n + extra), dim3(FUSE_THREADS), 0, s, a);
+        if (f.far_table) hipLaunchKernelGGL((k_fuse<FUSE_LCAP_FAR, true, false>), dim3(n + extra), dim3(FUSE_THREADS), 0, s, a);
         else hipLaunchKernelGGL((k_fuse<FUSE_LCAP_NEAR, true, false>), dim3(n + extra), dim3(FUSE_THREADS), 0, s, a);
-    } else if (far_table) hipLaunchKernelGGL((k_fuse<FUSE_LCAP_FAR, false, false>), dim3(n), dim3(FUSE_THREADS), 0, s, a);
-    else hipLaunchKernelGGL((k_fuse<FUSE_LCAP_NEAR, false, false>), dim3(n), dim3(FUSE_THREADS), GSDF_EXPERIMENT(debug, 4096) ? 81920 : 0, s, a);   /* experiment: 1 workgroup per CU */
-    if (resolve_follows)
-        hipLaunchKernelGGL(k_fuse_resolve, dim3(512), dim3(256), 0, s, deferred, deferred_count, deferred_cap, gate, st, ticket + 1);
+    } else if (f.far_table) hipLaunchKernelGGL((k_fuse<FUSE_LCAP_FAR, false, false>), dim3(n), dim3(FUSE_THREADS), 0, s, a);
+    else hipLaunchKernelGGL((k_fuse<FUSE_LCAP_NEAR, false, false>), dim3(n), dim3(FUSE_THREADS), GSDF_EXPERIMENT(f.debug, 4096) ? 81920 : 0, s, a);   /* experiment: 1 workgroup per CU */
+    if (f.resolve_follows)
+        hipLaunchKernelGGL(k_fuse_resolve, dim3(512), dim3(256), 0, s, f.deferred, f.deferred_count, f.deferred_cap, gate, f.st, f.ticket + 1);
 }
 int gsdf_fuse_grid_blocks(int W, int H) { return ((W + FUSE_T - 1) / FUSE_T) * ((H + FUSE_TH - 1) / FUSE_TH); }
 /* Launch order of the fusion tiles.  Colour-major (colour = parity of tile x, y): a tile only ever waits for tiles
