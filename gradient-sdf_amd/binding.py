@@ -81,6 +81,8 @@ def load_test_lib():
         f = getattr(L, name)
         f.restype = C.c_int
         f.argtypes = args
+    L.gsdf_debug_fail_alloc.restype = C.c_int           # process-wide: the nth owned allocation from now on fails once (0 disarms)
+    L.gsdf_debug_fail_alloc.argtypes = [C.c_int]
     return L
 
 

@@ -78,7 +78,7 @@ int status_to_code(int status) {
 
 int require_frame(gsdf_ctx* c) {
     if (!c) return fail(GSDF_ERR_INVALID, "null context");
-    if (!c->planes) return fail(GSDF_ERR_INVALID, "gsdf_normals_init must be called first (NEst == nullptr, MapGradPixelSdf.cpp:55-58)");
+    if (!c->frame.planes) return fail(GSDF_ERR_INVALID, "gsdf_normals_init must be called first (NEst == nullptr, MapGradPixelSdf.cpp:55-58)");
     return GSDF_OK;
 }
 
@@ -196,8 +196,8 @@ static int auto_grow_step(gsdf_ctx* c) {
 /* the tile statistics that belong to a set of normal planes (written by whatever computes the normals, read by the set's k_fuse) */
 static uint32_t* stats_of(const gsdf_ctx* c, const float* nrm) {
     const size_t N = (size_t)c->W * c->H;
-    const size_t set = (size_t)(nrm - c->normals) / (3 * N);
-    return c->tile_stats + set * (size_t)c->fuse_blocks * 4;
+    const size_t set = (size_t)(nrm - c->frame.normals) / (3 * N);
+    return c->frame.tile_stats + set * (size_t)c->fuse_blocks * 4;
 }
 
 /* one k_fuse launch: depth + its normal planes `nrm` (3 x N floats) -> the map.  next_depth (nullable): the launch's extra
@@ -213,20 +213,20 @@ int launch_fuse(gsdf_ctx* c, const float* depth_dev, const float* nrm, const gsd
         c->fuse_tag += 1;
         if (c->fuse_tag == 0) {                                /* wrapped: no stale flag may equal a new tag */
             c->fuse_tag = 1;
-            HIP_TRY(hipMemsetAsync(c->tile_flags, 0, (size_t)c->fuse_blocks * sizeof(unsigned int), c->stream));
+            HIP_TRY(hipMemsetAsync(c->frame.tile_flags, 0, (size_t)c->fuse_blocks * sizeof(unsigned int), c->stream));
         }
         gsdf_fuse_launch f;
         f.g = c->geom(); f.nc = c->ncache();
         f.depth = depth_dev; f.nx = nrm; f.ny = nrm + N; f.nz = nrm + 2 * N; f.tile_stats = stats_of(c, nrm);
         f.pose = pose; f.use_dev_pose = use_dev_pose;
-        f.tab = c->tab; f.st = c->st; f.blk_counters = c->blk_counters;
-        f.deferred = c->deferred; f.deferred_count = c->deferred_count; f.deferred_cap = c->deferred_cap;
-        f.tag = c->fuse_tag; f.tile_flags = c->tile_flags; f.tile_order = c->tile_order; f.ticket = c->fuse_ticket;
-        f.log_rows = c->frame_log; f.max_rows = c->frame_log_cap; f.vis = c->vis; f.vis_words = c->vis_words;
+        f.tab = c->tab; f.st = c->st; f.blk_counters = c->frame.blk_counters;
+        f.deferred = c->frame.deferred; f.deferred_count = c->frame.deferred_count; f.deferred_cap = c->deferred_cap;
+        f.tag = c->fuse_tag; f.tile_flags = c->frame.tile_flags; f.tile_order = c->frame.tile_order; f.ticket = c->frame.fuse_ticket;
+        f.log_rows = c->frame.frame_log; f.max_rows = c->frame_log_cap; f.vis = c->map.vis; f.vis_words = c->vis_words;
         f.debug = c->debug & 0xFFFF;
         /* long deferred lists lately (the note lags by a launch or two: a hint, not a condition) */
         f.resolve_follows = c->progress && c->progress[2] > 8192u ? 1 : 0;
-        f.host_note = c->progress ? c->progress_dev + 2 : nullptr;
+        f.host_note = c->progress ? c->progress.dev() + 2 : nullptr;
         /* many tiles did not fit the small LDS table lately (far geometry): the kernel with the larger one.  Like the note
          * above a hint that lags by a launch or two, never a condition for correctness; the caller read it once for the whole
          * frame entry (fuse_far_table) */
@@ -248,17 +248,17 @@ int enqueue_fuse(gsdf_ctx* c, const float* depth_dev, const gsdf_pose_arg& pose,
     const size_t N = (size_t)c->W * c->H;
     /* tracked frames: set 2, filled beside the first tracker passes -- or the set the PREVIOUS frame's fusion filled in its
      * tail (gsdf_hint_next_depth_dev) */
-    float* nrm = c->normals + (size_t)route.fuse_set * 3 * N;
+    float* nrm = c->frame.normals + (size_t)route.fuse_set * 3 * N;
     const float* next_depth = route.hint;
     if (!normals_done) {
-        nrm = c->normals + (size_t)c->ahead.take_gt_set() * 3 * N;
+        nrm = c->frame.normals + (size_t)c->ahead.take_gt_set() * 3 * N;
         prof_scope ps(c, 0);
         gsdf_launch_normals(c->stream, c->geom(), c->win, c->ncache(), depth_dev, nrm, nrm + N, nrm + 2 * N, nullptr, nullptr, stats_of(c, nrm));
         next_depth = nullptr;
     }
     /* gsdf_hint_next_depth_dev: the launch's last workgroups compute NormalEstimator::compute of the NEXT frame into set
      * next_set -- if the launch's gate is open -- and leave next_token in st->nrm_token */
-    float* next_nrm = next_depth ? c->normals + (size_t)route.next_set * 3 * N : nullptr;
+    float* next_nrm = next_depth ? c->frame.normals + (size_t)route.next_set * 3 * N : nullptr;
     return launch_fuse(c, depth_dev, nrm, pose, use_dev_pose, far_table, next_depth, next_nrm, head, route.next_token);
 }
 
@@ -327,9 +327,9 @@ int compact_sampled(track_frame& f, int sampling) {
     gsdf_ctx* c = f.c;
     if (f.fuse_after) return fail(GSDF_ERR_INVALID, "the frame loop tracks every pixel (RigidPointOptimizer.h:69-72)");
     const int Ws = (c->W + sampling - 1) / sampling, Hs = (c->H + sampling - 1) / sampling;
-    if (!c->depth_sampled) HIP_TRY(hipMalloc((void**)&c->depth_sampled, (size_t)((c->W + 1) / 2) * ((c->H + 1) / 2) * sizeof(float)));
-    gsdf_launch_subsample(c->stream, f.depth, c->W, c->H, sampling, c->depth_sampled);
-    f.depth = c->depth_sampled;
+    if (!c->frame.depth_sampled) HIP_TRY(c->frame.depth_sampled.alloc((size_t)((c->W + 1) / 2) * ((c->H + 1) / 2)));
+    gsdf_launch_subsample(c->stream, f.depth, c->W, c->H, sampling, c->frame.depth_sampled);
+    f.depth = c->frame.depth_sampled;
     f.g.W = Ws; f.g.H = Hs;
     return GSDF_OK;
 }
@@ -361,9 +361,9 @@ void track_jobs(track_frame& f, float conv, float damping, int sampling) {
     if (f.fuse_after) {                  /* the frame's normals ride along with its first passes (unless computed ahead: ride_token) */
         const size_t N = (size_t)c->W * c->H;
         f.nj.nc = c->ncache();
-        f.nj.nx = c->normals + (size_t)(3 * f.route.fuse_set) * N; f.nj.ny = f.nj.nx + N; f.nj.nz = f.nj.nx + 2 * N;    /* set 2, or the hinted one */
+        f.nj.nx = c->frame.normals + (size_t)(3 * f.route.fuse_set) * N; f.nj.ny = f.nj.nx + N; f.nj.nz = f.nj.nx + 2 * N;    /* set 2, or the hinted one */
         f.nj.token = f.route.ride_token;
-        f.nj.deferred_count = c->deferred_count;
+        f.nj.deferred_count = c->frame.deferred_count;
         f.nj.stats = stats_of(c, f.nj.nx);
         f.nj.r = c->win / 2; f.nj.ntx = 0;
         f.nj.tile_first = 0; f.nj.tile_count = 0;
@@ -378,7 +378,7 @@ void track_jobs(track_frame& f, float conv, float damping, int sampling) {
     f.adaptive = c->adaptive && c->progress;
     /* (the last launch index of this frame's first batch) */
     if (f.fuse_after) c->ahead.tracked(tp.serial, std::min(f.iters, (f.adaptive ? c->first_batch : f.iters + 1) - 1));
-    tp.progress = f.adaptive ? c->progress_dev : nullptr;
+    tp.progress = f.adaptive ? c->progress.dev() : nullptr;
     tp.debug = c->debug >> 16;
     tp.n_track_blocks = c->track_blocks;
     tp.sampling = sampling;
@@ -390,10 +390,10 @@ int track_one_launch(track_frame& f) {
     gsdf_ctx* c = f.c;
     f.tp.pass_index = 0;
     f.tp.rot = 0;
-    f.tp.progress = c->progress_dev;
+    f.tp.progress = c->progress.dev();
     {
         prof_scope ps(c, 2);
-        gsdf_launch_track_all(c->stream, f.g, f.depth, c->tab, c->st, c->track_rows, c->track_abort, c->track_blocks, f.tp,
+        gsdf_launch_track_all(c->stream, f.g, f.depth, c->tab, c->st, c->frame.track_rows, c->frame.track_abort, c->track_blocks, f.tp,
                               f.fuse_after ? &f.nj : nullptr);
     }
     if (f.fuse_after) {
@@ -436,7 +436,7 @@ int track_batched(track_frame& f, int base) {
                 f.nj.tile_first = lo; f.nj.tile_count = hi - lo; job = &f.nj;
             }
             prof_scope ps(c, 2);
-            gsdf_launch_track_pass(c->stream, f.g, f.depth, c->tab, c->st, c->partials, c->track_blocks, tp, job, base);
+            gsdf_launch_track_pass(c->stream, f.g, f.depth, c->tab, c->st, c->frame.partials, c->track_blocks, tp, job, base);
         }
         /* The fusion is queued behind the FIRST batch unseen (the usual frame ends there and must not wait for the host) and
          * behind the last one (nothing follows it).  Behind the batches in between it would nearly always be a gated launch
@@ -450,7 +450,7 @@ int track_batched(track_frame& f, int base) {
                 hd.k = last;
                 hd.rot_prev = (c->track_rot + 2u) % 3u;      /* the buffer the last launch issued (pass last - 1) accumulated into */
                 hd.conv_sq = tp.conv_sq; hd.damping = tp.damping; hd.max_passes = tp.max_passes;
-                hd.serial = tp.serial; hd.progress = tp.progress; hd.rows = c->partials; hd.debug = tp.debug;
+                hd.serial = tp.serial; hd.progress = tp.progress; hd.rows = c->frame.partials; hd.debug = tp.debug;
             }
             const int rc = f.queue_fusion(stand_in ? &hd : nullptr);
             if (rc) return rc;
@@ -495,12 +495,19 @@ int enqueue_track(gsdf_ctx* c, const float* depth_dev, int iters, float conv, fl
     track_jobs(f, conv, damping, sampling);
     const int base = c->map_type == GSDF_MAP_BASE;
     /* (k_track_all has the grad gather only: a base context runs the per-pass launches) */
-    if (sampling == 1 && !base && c->persist && c->track_rows && c->track_blocks <= 2 * GSDF_TRACK_MAXBLK) return track_one_launch(f);
+    if (sampling == 1 && !base && c->persist && c->frame.track_rows && c->track_blocks <= 2 * GSDF_TRACK_MAXBLK) return track_one_launch(f);
     const int rc = track_batched(f, base);
     if (rc) return rc;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(GSDF_ERR_HIP, std::string("tracking launch: ") + hipGetErrorString(e));
     return GSDF_OK;
+}
+
+/* alloc(count), and the zeroes queued on the stream */
+template <class T>
+hipError_t alloc_zeroed(gsdf_dev<T>& b, size_t count, hipStream_t s) {
+    const hipError_t e = b.alloc(count);
+    return e != hipSuccess ? e : hipMemsetAsync(b, 0, b.bytes(), s);
 }
 
 int read_state(gsdf_ctx* c, gsdf_dev_state* out) {
@@ -518,7 +525,7 @@ int gsdf_flush_pending(gsdf_ctx* c) {
     if (hipSetDevice(c->device) != hipSuccess) return fail(GSDF_ERR_HIP, "hipSetDevice");
     const size_t N = (size_t)c->W * c->H;
     const gsdf_lookahead::pending_fuse& p = c->ahead.pending;
-    return launch_fuse(c, p.depth, c->normals + (size_t)p.set * 3 * N, p.pose, 0, fuse_far_table(c), nullptr, nullptr);
+    return launch_fuse(c, p.depth, c->frame.normals + (size_t)p.set * 3 * N, p.pose, 0, fuse_far_table(c), nullptr, nullptr);
 }
 #define GSDF_FLUSH(c) do { if ((c) && (c)->ahead.pending.valid) { const int rc_ = gsdf_flush_pending(c); if (rc_) return rc_; } } while (0)
 /* The staging entries (gsdf_dev_upload*) write device memory the caller names.  A GT-pose fusion that still waits for its
@@ -548,9 +555,9 @@ int gsdf_debug_flags(gsdf_ctx* c, int flags) {
     c->debug = flags;
     if (flags & 64) {                                  /* k_fuse trace: GSDF_TRACE_COLS time stamps per workgroup, pointer in dbg[23] */
         if (hipStreamSynchronize(c->stream) != hipSuccess) return GSDF_ERR_HIP;
-        if (!c->trace && hipMalloc((void**)&c->trace, (size_t)GSDF_TRACE_WG * GSDF_TRACE_COLS * 8) != hipSuccess) return GSDF_ERR_HIP;
+        if (!c->trace && c->trace.alloc((size_t)GSDF_TRACE_WG * GSDF_TRACE_COLS) != hipSuccess) return GSDF_ERR_HIP;
         if (hipMemset(c->trace, 0, (size_t)GSDF_TRACE_WG * GSDF_TRACE_COLS * 8) != hipSuccess) return GSDF_ERR_HIP;
-        const unsigned long long ptr = (unsigned long long)(uintptr_t)c->trace;
+        const unsigned long long ptr = (unsigned long long)(uintptr_t)c->trace.get();
         if (hipMemcpy(&c->st->dbg[23], &ptr, 8, hipMemcpyHostToDevice) != hipSuccess) return GSDF_ERR_HIP;
     }
     return GSDF_OK;
@@ -566,7 +573,7 @@ int gsdf_debug_trace(gsdf_ctx* c, unsigned long long* out, int n_wg) {
 /* the raycaster's per-workgroup rows (8 values each, see gsdf_launch_raycast), tools/raycast_bench.py */
 int gsdf_debug_raycast_rows(gsdf_ctx* c, unsigned long long* out, int n_rows) {
     GSDF_FLUSH(c);
-    if (!c || !out || !c->rc_counts || (size_t)n_rows > c->rc_rows) return GSDF_ERR_INVALID;
+    if (!c || !out || !c->rc_counts || (size_t)n_rows > c->rc_counts.count() / 8) return GSDF_ERR_INVALID;
     if (hipStreamSynchronize(c->stream) != hipSuccess) return GSDF_ERR_HIP;
     if (hipMemcpy(out, c->rc_counts, (size_t)n_rows * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return GSDF_ERR_HIP;
     return GSDF_OK;
@@ -575,21 +582,21 @@ int gsdf_debug_raycast_rows(gsdf_ctx* c, unsigned long long* out, int n_rows) {
  * n_valid, totals) and a caller-made order (same encoding as gsdf_fuse_tile_order; n = workgroups) */
 int gsdf_debug_tile_counters(gsdf_ctx* c, unsigned long long* out, int n_rows) {
     GSDF_FLUSH(c);
-    if (!c || !out || !c->blk_counters || n_rows > c->fuse_blocks) return GSDF_ERR_INVALID;
+    if (!c || !out || !c->frame.blk_counters || n_rows > c->fuse_blocks) return GSDF_ERR_INVALID;
     if (hipStreamSynchronize(c->stream) != hipSuccess) return GSDF_ERR_HIP;
-    if (hipMemcpy(out, c->blk_counters, (size_t)n_rows * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return GSDF_ERR_HIP;
+    if (hipMemcpy(out, c->frame.blk_counters, (size_t)n_rows * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return GSDF_ERR_HIP;
     return GSDF_OK;
 }
 int gsdf_debug_set_tile_order(gsdf_ctx* c, const uint32_t* order, int n) {
     GSDF_FLUSH(c);
-    if (!c || !order || !c->tile_order || n != c->fuse_blocks) return GSDF_ERR_INVALID;
+    if (!c || !order || !c->frame.tile_order || n != c->fuse_blocks) return GSDF_ERR_INVALID;
     if (hipStreamSynchronize(c->stream) != hipSuccess) return GSDF_ERR_HIP;
-    if (hipMemcpy(c->tile_order, order, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return GSDF_ERR_HIP;
+    if (hipMemcpy(c->frame.tile_order, order, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return GSDF_ERR_HIP;
     return GSDF_OK;
 }
 int gsdf_debug_get_tile_order(gsdf_ctx* c, uint32_t* order, int* n) {
-    if (!c || !order || !n || !c->tile_order) return GSDF_ERR_INVALID;
-    if (hipMemcpy(order, c->tile_order, (size_t)c->fuse_blocks * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return GSDF_ERR_HIP;
+    if (!c || !order || !n || !c->frame.tile_order) return GSDF_ERR_INVALID;
+    if (hipMemcpy(order, c->frame.tile_order, (size_t)c->fuse_blocks * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return GSDF_ERR_HIP;
     *n = c->fuse_blocks;
     return GSDF_OK;
 }
@@ -605,6 +612,14 @@ int gsdf_debug_read(gsdf_ctx* c, unsigned long long out[24]) {
 /* normals_tile_split as enqueue_track uses it, for the tests: no context, no device.  1 = launch k computes the tiles [*lo, *hi) */
 int gsdf_debug_normals_tile_split(int tiles, int k, int launches, int iters, int batch, int nrm_split, int nrm_split2, int* lo, int* hi) {
     return lo && hi && normals_tile_split(tiles, k, launches, iters, batch, nrm_split, nrm_split2, lo, hi) ? 1 : 0;
+}
+/* The nth allocation the owning types (gsdf_dev.h) make from now on fails once with hipErrorOutOfMemory, without calling the
+ * runtime; 0 disarms.  Returns the owned allocations made since the previous call.  Process-wide. */
+int gsdf_debug_fail_alloc(int nth) {
+    const int made = g_gsdf_alloc_count;
+    g_gsdf_alloc_count = 0;
+    g_gsdf_alloc_fail_at = nth > 0 ? nth : 0;
+    return made;
 }
 const char* gsdf_version(void) { return "gsdf-mi355x 0.2 (gfx950) +experiments"; }
 #else
@@ -665,12 +680,7 @@ static int create_impl(gsdf_ctx** out, float voxel_size, float trunc_dist, int c
     }
     if ((e = (other_queue ? hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_greatest)
                           : hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking))) != hipSuccess ||
-        (e = hipMalloc((void**)&c->tab.vox, c->n_slots * sizeof(gsdf_payload))) != hipSuccess ||
-        (e = hipMalloc((void**)&c->tab.bkeys, (c->n_slots / GSDF_BLOCK_VOX) * sizeof(unsigned long long))) != hipSuccess ||
-        /* block filter (64 bits per block entry) followed by the cell filter (1 bit per block entry, at least one word) */
-        (e = hipMalloc((void**)&c->tab.occ, c->n_slots / 8 + std::max<size_t>(c->n_slots / GSDF_BLOCK_VOX / 8, 4))) != hipSuccess ||
-        (e = hipMalloc((void**)&c->st, sizeof(gsdf_dev_state))) != hipSuccess ||
-        (e = hipMalloc((void**)&c->counter, sizeof(unsigned long long))) != hipSuccess ||
+        (e = c->map.alloc(c->n_slots, 0)) != hipSuccess || (e = c->st.alloc(1)) != hipSuccess || (e = c->counter.alloc(1)) != hipSuccess ||
         (e = hipEventCreate(&c->ev0)) != hipSuccess || (e = hipEventCreate(&c->ev1)) != hipSuccess) {
         std::string m = std::string("gsdf_create: ") + hipGetErrorString(e);
         gsdf_destroy(c);
@@ -680,16 +690,9 @@ static int create_impl(gsdf_ctx** out, float voxel_size, float trunc_dist, int c
         const char* env = getenv("GSDF_DEFER");                    /* 0: every gsdf_update_dev launches its normals and its fusion at once */
         if (env) c->defer = atoi(env);
     }
-    c->tab.block_mask = (uint32_t)(c->n_slots / GSDF_BLOCK_VOX - 1);
+    c->tab = c->map.table(c->n_slots);
     {
-        void* hp = nullptr;
-        if (hipHostMalloc(&hp, 64, hipHostMallocMapped) == hipSuccess) {
-            std::memset(hp, 0, 64);
-            void* dp = nullptr;
-            if (hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) { c->progress = (volatile unsigned int*)hp; c->progress_dev = (unsigned int*)dp; }
-            else (void)hipHostFree(hp);
-        }
-        (void)hipGetLastError();
+        if (c->progress.alloc(16) != hipSuccess) (void)hipGetLastError();   /* optional: without them no adaptive batches, no auto-grow */
         const char* env = getenv("GSDF_ADAPTIVE");
         if (env) c->adaptive = atoi(env);
         if ((env = getenv("GSDF_FIRST_BATCH")) && atoi(env) >= 2) c->first_batch = atoi(env);
@@ -718,9 +721,7 @@ void gsdf_destroy(gsdf_ctx* c) {
     if (!c) return;
     (void)gsdf_flush_pending(c);
     (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->trace) { (void)hipFree(c->trace); c->trace = nullptr; }      /* after the sync: a running kernel may still write stamps */
-    gsdf_color_release(c);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);    /* the context's buffers go with it: nothing may still run on them */
     prof_collect(c);
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
     for (auto& u : c->uploads) { (void)hipEventSynchronize(u.second); (void)hipEventDestroy(u.second); }
@@ -728,12 +729,6 @@ void gsdf_destroy(gsdf_ctx* c) {
     for (hipEvent_t e : c->mark_pool) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->upload_pool) (void)hipEventDestroy(e);
     for (auto& m : c->marks) (void)hipEventDestroy(m.second);
-    void* ptrs[] = { c->depth_sampled, c->tile_stats, c->grow_scratch, c->scratch, c->track_rows, c->track_abort, c->rc_counts, c->tab.vox, c->tab.bkeys, c->tab.occ, c->st, c->counter, c->planes, c->depth_stage, c->normals, c->partials,
-                     c->blk_counters, c->frame_log, c->deferred, c->deferred_count, c->fuse_ticket, c->tile_flags, c->tile_order, c->vis, c->ba_images, c->ba_Rt,
-                     c->ba_frame_idx, c->ba_block_E, c->ba_block_part, c->ba_Hb, c->ba_gate_list, c->ba_gate_tmp, c->counter2, c->ba_mean };
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (auto& b : c->mx) if (b.p) (void)hipFree(b.p);
-    if (c->progress) (void)hipHostFree((void*)c->progress);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -745,22 +740,22 @@ int gsdf_reset(gsdf_ctx* c) {
     HIP_TRY(hipSetDevice(c->device));
     c->ahead.forget_all();                                 /* a fusion that was never launched is dropped with the map; gsdf_hint_next_depth_dev: a new scan starts without them */
     c->fuse_launches = 0; c->far_table_launches = 0;
-    if (c->deferred_count) HIP_TRY(hipMemsetAsync(c->deferred_count, 0, sizeof(unsigned int), c->stream));
+    if (c->frame.deferred_count) HIP_TRY(hipMemsetAsync(c->frame.deferred_count, 0, sizeof(unsigned int), c->stream));
     gsdf_launch_table_clear(c->stream, c->tab, c->n_slots);
-    if (c->vis) HIP_TRY(hipMemsetAsync(c->vis, 0, c->n_slots * (size_t)c->vis_words * sizeof(uint32_t), c->stream));
+    if (c->map.vis) HIP_TRY(hipMemsetAsync(c->map.vis, 0, c->n_slots * (size_t)c->vis_words * sizeof(uint32_t), c->stream));
     HIP_TRY(hipMemsetAsync(c->st, 0, sizeof(gsdf_dev_state), c->stream));
     if (c->trace) {                                          /* test build: the memset cleared the trace pointer kept in dbg[23] */
-        const unsigned long long ptr = (unsigned long long)(uintptr_t)c->trace;
+        const unsigned long long ptr = (unsigned long long)(uintptr_t)c->trace.get();
         HIP_TRY(hipMemcpyAsync(&c->st->dbg[23], &ptr, 8, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));            /* `ptr` is a stack variable */
     }
     const float ident[7] = { 0, 0, 0, 0, 0, 0, 1 };          /* pose_ = SE3() -- RigidOptimizer.h:64 */
     gsdf_launch_set_pose(c->stream, c->st, nullptr, ident);
-    if (c->blk_counters)
-        HIP_TRY(hipMemsetAsync(c->blk_counters, 0, (size_t)c->fuse_blocks * 4 * sizeof(unsigned long long), c->stream));
+    if (c->frame.blk_counters)
+        HIP_TRY(hipMemsetAsync(c->frame.blk_counters, 0, (size_t)c->fuse_blocks * 4 * sizeof(unsigned long long), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->merged = false;
-    gsdf_color_drop(c);                                      /* the ColorUpsampler snapshot describes the old map */
+    c->color.drop();                                         /* the ColorUpsampler snapshot describes the old map */
     c->grow_forget = true;                                   /* auto-grow's block counts describe the old map (a grown table keeps its size) */
     c->occ_dirty = false;                                    /* the table clear zeroed the filters as well */
     return GSDF_OK;
@@ -791,7 +786,7 @@ int gsdf_set_auto_grow(gsdf_ctx* c, int max_capacity_log2) {
         return fail(GSDF_ERR_INVALID, "gsdf_set_auto_grow: 0 (off) or a capacity_log2 between the present one and 30");
     HIP_TRY(hipSetDevice(c->device));
     if (max_capacity_log2 && !c->grow_scratch) {
-        HIP_TRY(hipMalloc((void**)&c->grow_scratch, 2 * sizeof(unsigned int)));
+        HIP_TRY(c->grow_scratch.alloc(2));
         HIP_TRY(hipMemsetAsync(c->grow_scratch, 0, 2 * sizeof(unsigned int), c->stream));
     }
     if (max_capacity_log2 && !c->progress) return fail(GSDF_ERR_HIP, "gsdf_set_auto_grow: no pinned progress words on this context");
@@ -827,67 +822,55 @@ int gsdf_normals_init(gsdf_ctx* c, int W, int H, const float K[9], int win) {
         return fail(GSDF_ERR_INVALID, "W,H > 0 and odd window <= 15 required");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    void* old[] = { c->depth_sampled, c->tile_stats, c->planes, c->depth_stage, c->normals, c->partials, c->blk_counters, c->frame_log, c->deferred,
-                    c->deferred_count, c->tile_flags, c->tile_order, c->fuse_ticket, c->track_rows, c->track_abort };
-    for (void* p : old) if (p) (void)hipFree(p);
-    c->track_rows = nullptr; c->track_abort = nullptr;
-    c->tile_flags = nullptr; c->tile_order = nullptr; c->tile_stats = nullptr;
-    c->planes = c->depth_stage = c->normals = nullptr; c->partials = nullptr; c->depth_sampled = nullptr;
+    c->frame = gsdf_frame_bufs();                            /* the old frame goes first (peak memory); until the commit below there is none */
     c->ahead.forget_frames();
-    c->blk_counters = nullptr; c->frame_log = nullptr; c->deferred = nullptr; c->deferred_count = nullptr; c->fuse_ticket = nullptr;
-    c->W = W; c->H = H; c->win = win;
-    std::memcpy(c->K, K, 9 * sizeof(float));
+    gsdf_frame_bufs f;
     const size_t N = (size_t)W * H;
-    HIP_TRY(hipMalloc((void**)&c->planes, 11 * N * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&c->depth_stage, N * sizeof(float)));
+    HIP_TRY(f.planes.alloc(11 * N));
+    HIP_TRY(f.depth_stage.alloc(N));
     /* three sets of 3 planes: sets 0 / 1 alternate between GT-pose fusions (the normals of frame i + 1 are computed on a second
      * stream while frame i is being fused), set 2 belongs to the main stream (tracked frames, gsdf_normals_compute) */
-    HIP_TRY(hipMalloc((void**)&c->normals, 3 * 3 * N * sizeof(float)));
+    HIP_TRY(f.normals.alloc(3 * 3 * N));
     /* tracker grid: a multiple of the 256 CUs when the frame is large enough, 1-4 pixels per lane */
-    c->track_blocks = N >= (size_t)1 << 20 ? 2 * GSDF_TRACK_MAXBLK : N >= (size_t)1 << 18 ? GSDF_TRACK_MAXBLK
-                                                : (int)std::max<size_t>(1, (N + 511) / 512);
-    HIP_TRY(hipMalloc((void**)&c->partials, (size_t)3 * GSDF_TRACK_ROWSET * sizeof(double)));
-    HIP_TRY(hipMemsetAsync(c->partials, 0, (size_t)3 * GSDF_TRACK_ROWSET * sizeof(double), c->stream));
-    c->track_rot = 0;
-    if (c->track_blocks <= 2 * GSDF_TRACK_MAXBLK) {
-        HIP_TRY(hipMalloc(&c->track_rows, gsdf_track_all_rows_bytes(c->track_blocks)));
-        HIP_TRY(hipMemsetAsync(c->track_rows, 0, gsdf_track_all_rows_bytes(c->track_blocks), c->stream));
-        HIP_TRY(hipMalloc((void**)&c->track_abort, sizeof(unsigned int)));
-        HIP_TRY(hipMemsetAsync(c->track_abort, 0, sizeof(unsigned int), c->stream));
+    const int track_blocks = N >= (size_t)1 << 20 ? 2 * GSDF_TRACK_MAXBLK : N >= (size_t)1 << 18 ? GSDF_TRACK_MAXBLK
+                                                  : (int)std::max<size_t>(1, (N + 511) / 512);
+    HIP_TRY(alloc_zeroed(f.partials, (size_t)3 * GSDF_TRACK_ROWSET, c->stream));
+    if (track_blocks <= 2 * GSDF_TRACK_MAXBLK) {
+        HIP_TRY(alloc_zeroed(f.track_rows, gsdf_track_all_rows_bytes(track_blocks), c->stream));
+        HIP_TRY(alloc_zeroed(f.track_abort, 1, c->stream));
     }
-    c->fuse_blocks = gsdf_fuse_grid_blocks(W, H);
+    const int fuse_blocks = gsdf_fuse_grid_blocks(W, H);
     /* per set of normal planes: the statistics of the frame's fusion tiles (depth range, valid pixels), written with the normals */
-    HIP_TRY(hipMalloc((void**)&c->tile_stats, (size_t)3 * c->fuse_blocks * 4 * sizeof(uint32_t)));
-    HIP_TRY(hipMemsetAsync(c->tile_stats, 0, (size_t)3 * c->fuse_blocks * 4 * sizeof(uint32_t), c->stream));
-    HIP_TRY(hipMalloc((void**)&c->blk_counters, (size_t)c->fuse_blocks * 4 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(c->blk_counters, 0, (size_t)c->fuse_blocks * 4 * sizeof(unsigned long long), c->stream));
-    HIP_TRY(hipMalloc((void**)&c->tile_flags, (size_t)c->fuse_blocks * sizeof(unsigned int)));
-    HIP_TRY(hipMemsetAsync(c->tile_flags, 0, (size_t)c->fuse_blocks * sizeof(unsigned int), c->stream));
+    HIP_TRY(alloc_zeroed(f.tile_stats, (size_t)3 * fuse_blocks * 4, c->stream));
+    HIP_TRY(alloc_zeroed(f.blk_counters, (size_t)fuse_blocks * 4, c->stream));
+    HIP_TRY(alloc_zeroed(f.tile_flags, (size_t)fuse_blocks, c->stream));
     {
-        std::vector<uint32_t> order((size_t)c->fuse_blocks);
+        std::vector<uint32_t> order((size_t)fuse_blocks);
         gsdf_fuse_tile_order(W, H, order.data());
-        HIP_TRY(hipMalloc((void**)&c->tile_order, order.size() * sizeof(uint32_t)));
-        HIP_TRY(hipMemcpy(c->tile_order, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(f.tile_order.alloc(order.size()));
+        HIP_TRY(hipMemcpy(f.tile_order, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     /* deferred list: contributions of near tiles and LDS overflow; bounded by the samples of a frame */
-    c->deferred_cap = (unsigned int)std::min<size_t>((size_t)1 << 26, std::max<size_t>((size_t)1 << 18,
-                                                     N * (size_t)(2 * c->factor + 1)));   /* every sample of a frame */
-    HIP_TRY(hipMalloc((void**)&c->deferred, (size_t)c->deferred_cap * sizeof(gsdf_deferred)));
-    HIP_TRY(hipMalloc((void**)&c->deferred_count, sizeof(unsigned int)));
-    HIP_TRY(hipMemsetAsync(c->deferred_count, 0, sizeof(unsigned int), c->stream));
-    HIP_TRY(hipMalloc((void**)&c->fuse_ticket, 2 * sizeof(unsigned int)));
-    HIP_TRY(hipMemsetAsync(c->fuse_ticket, 0, 2 * sizeof(unsigned int), c->stream));
-    c->frame_log_cap = 1 << 16;
-    HIP_TRY(hipMalloc((void**)&c->frame_log, (size_t)c->frame_log_cap * 10 * sizeof(float)));
+    const unsigned int deferred_cap = (unsigned int)std::min<size_t>((size_t)1 << 26, std::max<size_t>((size_t)1 << 18,
+                                                                     N * (size_t)(2 * c->factor + 1)));   /* every sample of a frame */
+    HIP_TRY(f.deferred.alloc(deferred_cap));
+    HIP_TRY(alloc_zeroed(f.deferred_count, 1, c->stream));
+    HIP_TRY(alloc_zeroed(f.fuse_ticket, 2, c->stream));
+    const long long frame_log_cap = 1 << 16;
+    HIP_TRY(f.frame_log.alloc((size_t)frame_log_cap * 10));
     {
-        double* scratch = nullptr;                           /* the row sums of the six moment planes, in double */
-        HIP_TRY(hipMalloc((void**)&scratch, gsdf_normals_cache_scratch_bytes(W, H)));
-        gsdf_launch_normals_cache(c->stream, W, H, c->K, win, c->planes, scratch);
-        const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(c->stream);
-        (void)hipFree(scratch);
-        HIP_TRY(e1);
-        HIP_TRY(e2);
+        gsdf_dev<void> scratch;                              /* the row sums of the six moment planes, in double */
+        HIP_TRY(scratch.alloc(gsdf_normals_cache_scratch_bytes(W, H)));
+        gsdf_launch_normals_cache(c->stream, W, H, K, win, f.planes, scratch.as<double>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(c->stream));
     }
+    /* the commit: only a complete frame, with the numbers that describe it, reaches the context */
+    c->frame = std::move(f);
+    c->W = W; c->H = H; c->win = win;
+    std::memcpy(c->K, K, 9 * sizeof(float));
+    c->track_blocks = track_blocks; c->track_rot = 0;
+    c->fuse_blocks = fuse_blocks; c->deferred_cap = deferred_cap; c->frame_log_cap = frame_log_cap;
     return GSDF_OK;
 }
 
@@ -896,7 +879,7 @@ int gsdf_normals_cache(gsdf_ctx* c, float* planes11_host) {
     int rc = require_frame(c);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(planes11_host, c->planes, 11 * (size_t)c->W * c->H * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(planes11_host, c->frame.planes, 11 * (size_t)c->W * c->H * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return GSDF_OK;
 }
@@ -907,9 +890,9 @@ int gsdf_normals_compute(gsdf_ctx* c, const float* depth_host, float* nx, float*
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const size_t N = (size_t)c->W * c->H;
-    HIP_TRY(hipMemcpyAsync(c->depth_stage, depth_host, N * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    float* set2 = c->normals + 6 * N;
-    gsdf_launch_normals(c->stream, c->geom(), c->win, c->ncache(), c->depth_stage, set2, set2 + N, set2 + 2 * N, nullptr, nullptr, stats_of(c, set2));
+    HIP_TRY(hipMemcpyAsync(c->frame.depth_stage, depth_host, N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    float* set2 = c->frame.normals + 6 * N;
+    gsdf_launch_normals(c->stream, c->geom(), c->win, c->ncache(), c->frame.depth_stage, set2, set2 + N, set2 + 2 * N, nullptr, nullptr, stats_of(c, set2));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(nx, set2, N * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(ny, set2 + N, N * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -941,13 +924,13 @@ int gsdf_update_dev(gsdf_ctx* c, const float* depth_dev, const float R[9], const
      * The two sets of normal planes alternate. */
     const size_t N = (size_t)c->W * c->H;
     const int set = c->ahead.take_gt_set();                /* sets 0 / 1 are this path's: a hinted tracked frame's normals are gone */
-    float* nrm = c->normals + (size_t)set * 3 * N;
+    float* nrm = c->frame.normals + (size_t)set * 3 * N;
     if (!c->ahead.pending.valid) {
         gsdf_launch_normals(c->stream, c->geom(), c->win, c->ncache(), depth_dev, nrm, nrm + N, nrm + 2 * N, nullptr, nullptr, stats_of(c, nrm));
         HIP_TRY(hipGetLastError());
     } else {
         const gsdf_lookahead::pending_fuse& p = c->ahead.pending;
-        int rc = launch_fuse(c, p.depth, c->normals + (size_t)p.set * 3 * N, p.pose, 0, fuse_far_table(c), depth_dev, nrm);
+        int rc = launch_fuse(c, p.depth, c->frame.normals + (size_t)p.set * 3 * N, p.pose, 0, fuse_far_table(c), depth_dev, nrm);
         c->ahead.release();
         if (rc) return rc;
     }
@@ -961,8 +944,8 @@ int gsdf_update(gsdf_ctx* c, const float* depth_host, const float R[9], const fl
     if (rc) return rc;
     if (!depth_host) return fail(GSDF_ERR_INVALID, "null depth");
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(c->depth_stage, depth_host, (size_t)c->W * c->H * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    rc = gsdf_update_dev(c, c->depth_stage, R, t);
+    HIP_TRY(hipMemcpyAsync(c->frame.depth_stage, depth_host, (size_t)c->W * c->H * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    rc = gsdf_update_dev(c, c->frame.depth_stage, R, t);
     if (rc) return rc;
     return gsdf_sync(c);
 }
@@ -1004,9 +987,9 @@ int gsdf_track_sampled(gsdf_ctx* c, const float* depth_host, const float K[9], f
     if (std::memcmp(K, c->K, 9 * sizeof(float)) != 0)
         return fail(GSDF_ERR_INVALID, "K differs from the intrinsics given to gsdf_normals_init");
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(c->depth_stage, depth_host, (size_t)c->W * c->H * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->frame.depth_stage, depth_host, (size_t)c->W * c->H * sizeof(float), hipMemcpyHostToDevice, c->stream));
     gsdf_launch_set_pose(c->stream, c->st, nullptr, pose7);
-    rc = enqueue_track(c, c->depth_stage, num_iterations, conv_threshold, damping, false, sampling);
+    rc = enqueue_track(c, c->frame.depth_stage, num_iterations, conv_threshold, damping, false, sampling);
     if (rc) return rc;
     gsdf_dev_state s;
     rc = read_state(c, &s);
@@ -1059,7 +1042,7 @@ int gsdf_read_frame_log(gsdf_ctx* c, float* rows10, int64_t max_rows, int64_t* n
     if (n_rows) *n_rows = n;
     n = std::min<int64_t>(n, max_rows);
     if (n > 0 && rows10) {
-        HIP_TRY(hipMemcpyAsync(rows10, c->frame_log, (size_t)n * 10 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(rows10, c->frame.frame_log, (size_t)n * 10 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return GSDF_OK;
@@ -1084,9 +1067,9 @@ int gsdf_get_stats(gsdf_ctx* c, gsdf_stats* out) {
     int rc = read_state(c, &s);
     if (rc) return rc;
     std::memset(out, 0, sizeof(*out));
-    if (c->blk_counters) {
+    if (c->frame.blk_counters) {
         std::vector<unsigned long long> h((size_t)c->fuse_blocks * 4);
-        HIP_TRY(hipMemcpy(h.data(), c->blk_counters, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h.data(), c->frame.blk_counters, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         unsigned long long cu = 0, cv = 0;
         for (int b = 0; b < c->fuse_blocks; ++b) { cu += h[4 * b + 2]; cv += h[4 * b + 3]; }
         out->n_upd = (int64_t)cu;
@@ -1131,11 +1114,8 @@ int gsdf_enable_vis(gsdf_ctx* c, int max_frames) {
     if (!c || max_frames <= 0) return fail(GSDF_ERR_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->vis) { (void)hipFree(c->vis); c->vis = nullptr; }
     c->vis_words = (max_frames + 31) / 32;
-    const size_t bytes = c->n_slots * (size_t)c->vis_words * sizeof(uint32_t);
-    HIP_TRY(hipMalloc((void**)&c->vis, bytes));
-    HIP_TRY(hipMemsetAsync(c->vis, 0, bytes, c->stream));
+    HIP_TRY(alloc_zeroed(c->map.vis, c->n_slots * (size_t)c->vis_words, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return GSDF_OK;
 }
@@ -1143,7 +1123,7 @@ int gsdf_enable_vis(gsdf_ctx* c, int max_frames) {
 int gsdf_export_vis(gsdf_ctx* c, int32_t* keys, uint32_t* words, int words_per_voxel, int64_t max_n, int64_t* n_out) {
     GSDF_FLUSH(c);
     if (!c || !words) return fail(GSDF_ERR_INVALID, "null argument");
-    if (!c->vis) return fail(GSDF_ERR_INVALID, "gsdf_enable_vis was not called");
+    if (!c->map.vis) return fail(GSDF_ERR_INVALID, "gsdf_enable_vis was not called");
     if (words_per_voxel != c->vis_words) return fail(GSDF_ERR_INVALID, "words_per_voxel differs from gsdf_enable_vis");
     return export_impl(c, keys, nullptr, words, max_n, n_out, 1, 0);
 }
@@ -1158,30 +1138,22 @@ static int export_impl(gsdf_ctx* c, int32_t* keys, float* payload, uint32_t* vis
     if (n_out) *n_out = n;
     if (n == 0 || max_n <= 0 || (!keys && !payload && !vis_words_out)) return GSDF_OK;
     if (max_n < n) return fail(GSDF_ERR_INVALID, "export buffer too small (call gsdf_count first)");
-    unsigned long long* dkeys = nullptr;
-    float* dpay = nullptr;
-    HIP_TRY(hipMalloc((void**)&dkeys, (size_t)n * sizeof(unsigned long long)));
-    hipError_t e = hipMalloc((void**)&dpay, (size_t)n * 5 * sizeof(float));
-    if (e != hipSuccess) { (void)hipFree(dkeys); return fail(GSDF_ERR_HIP, hipGetErrorString(e)); }
-    uint32_t* dvis = nullptr;
+    gsdf_dev<unsigned long long> dkeys;
+    gsdf_dev<float> dpay;
+    gsdf_dev<uint32_t> dvis;
     const int vw = vis_words_out ? c->vis_words : 0;
-    if (vw) {
-        e = hipMalloc((void**)&dvis, (size_t)n * vw * sizeof(uint32_t));
-        if (e != hipSuccess) { (void)hipFree(dkeys); (void)hipFree(dpay); return fail(GSDF_ERR_HIP, hipGetErrorString(e)); }
-    }
+    HIP_TRY(dkeys.alloc((size_t)n));
+    HIP_TRY(dpay.alloc((size_t)n * 5));
+    if (vw) HIP_TRY(dvis.alloc((size_t)n * vw));
     (void)hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream);
-    gsdf_launch_export(c->stream, c->tab, c->n_slots, dkeys, dpay, c->counter, n, raw_sums, c->vis, vw, dvis);
+    gsdf_launch_export(c->stream, c->tab, c->n_slots, dkeys, dpay, c->counter, n, raw_sums, c->map.vis, vw, dvis);
     std::vector<unsigned long long> hk((size_t)n);
     std::vector<float> hp((size_t)n * 5);
     std::vector<uint32_t> hv((size_t)n * vw);
-    e = hipMemcpyAsync(hk.data(), dkeys, hk.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(hp.data(), dpay, hp.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && vw) e = hipMemcpyAsync(hv.data(), dvis, hv.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(dkeys);
-    (void)hipFree(dpay);
-    if (dvis) (void)hipFree(dvis);
-    if (e != hipSuccess) return fail(GSDF_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(hk.data(), dkeys, hk.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(hp.data(), dpay, hp.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (vw) HIP_TRY(hipMemcpyAsync(hv.data(), dvis, hv.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     std::vector<size_t> order((size_t)n);
     std::iota(order.begin(), order.end(), (size_t)0);
     if (sorted)   /* packed keys order like (z, y, x) */
@@ -1204,21 +1176,15 @@ int gsdf_merge_raw(gsdf_ctx* c, const int32_t* keys, const float* payload_raw, i
     if (!c || (n > 0 && (!keys || !payload_raw))) return fail(GSDF_ERR_INVALID, "null argument");
     if (n <= 0) return GSDF_OK;
     HIP_TRY(hipSetDevice(c->device));
-    int32_t* dk = nullptr;
-    float* dp = nullptr;
-    HIP_TRY(hipMalloc((void**)&dk, (size_t)n * 3 * sizeof(int32_t)));
-    hipError_t e = hipMalloc((void**)&dp, (size_t)n * 5 * sizeof(float));
-    if (e != hipSuccess) { (void)hipFree(dk); return fail(GSDF_ERR_HIP, hipGetErrorString(e)); }
-    e = hipMemcpyAsync(dk, keys, (size_t)n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dp, payload_raw, (size_t)n * 5 * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        c->occ_dirty = true;
-        gsdf_launch_merge_raw(c->stream, c->tab, dk, dp, n, c->st);
-        e = hipStreamSynchronize(c->stream);
-    }
-    (void)hipFree(dk);
-    (void)hipFree(dp);
-    if (e != hipSuccess) return fail(GSDF_ERR_HIP, hipGetErrorString(e));
+    gsdf_dev<int32_t> dk;
+    gsdf_dev<float> dp;
+    HIP_TRY(dk.alloc((size_t)n * 3));
+    HIP_TRY(dp.alloc((size_t)n * 5));
+    HIP_TRY(hipMemcpyAsync(dk, keys, (size_t)n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dp, payload_raw, (size_t)n * 5 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    c->occ_dirty = true;
+    gsdf_launch_merge_raw(c->stream, c->tab, dk, dp, n, c->st);
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return gsdf_sync(c);
 }
 
@@ -1250,28 +1216,28 @@ int gsdf_merge_raw_dev(gsdf_ctx* c, const int32_t* keys_dev, const float* payloa
 /* ---- PhotoBA: PhotometricOptimizer (ps_optimizer/PhotometricOptimizer.cpp) ------------------------------- */
 static gsdf_ba_dev ba_dev(gsdf_ctx* c) {
     gsdf_ba_dev d;
-    d.tab = c->tab; d.n_slots = c->n_slots; d.vis = c->vis; d.vis_words = c->vis_words;
+    d.tab = c->tab; d.n_slots = c->n_slots; d.vis = c->map.vis; d.vis_words = c->vis_words;
     d.n = c->ba_n; d.W = c->W; d.H = c->H;
-    d.images = c->ba_images; d.R = c->ba_Rt; d.t = c->ba_Rt + 9 * (size_t)c->ba_n; d.frame_idx = c->ba_frame_idx;
+    d.images = c->ba.images; d.R = c->ba.Rt; d.t = c->ba.Rt + 9 * (size_t)c->ba_n; d.frame_idx = c->ba.frame_idx;
     d.fx = c->K[0]; d.fy = c->K[4]; d.cx = c->K[2]; d.cy = c->K[5]; d.vs = c->voxel_size; d.reg_weight = c->ba_reg;
     d.trunc_sq = c->ba_trunc_sq;
-    d.gate_list = c->ba_gate_fresh ? c->ba_gate_list : nullptr;
-    d.gate_count = c->counter2;
-    d.mean_cache = c->ba_mean;
+    d.gate_list = c->ba_gate_fresh ? c->ba.gate_list : nullptr;
+    d.gate_count = c->ba.counter2;
+    d.mean_cache = c->ba.mean;
     return d;
 }
 /* (re)builds the list of the voxels inside the |dist| <= vs gate, if the distances may have changed since it was made.  Enqueue
  * only; failures leave the sweeps on their whole-table form (gate_list == nullptr). */
 static void ba_refresh_gate(gsdf_ctx* c) {
-    if (c->ba_gate_fresh || !c->ba_gate_list || !c->counter2) return;
+    if (c->ba_gate_fresh || !c->ba.gate_list || !c->ba.counter2) return;
     gsdf_ba_dev d = ba_dev(c);
-    size_t bytes = c->ba_gate_tmp_bytes;
-    if (gsdf_ba_compact(c->stream, d, c->ba_gate_list, c->counter2, c->ba_gate_tmp, &bytes) == hipSuccess) c->ba_gate_fresh = true;
+    size_t bytes = c->ba.gate_tmp.bytes();
+    if (gsdf_ba_compact(c->stream, d, c->ba.gate_list, c->ba.counter2, c->ba.gate_tmp, &bytes) == hipSuccess) c->ba_gate_fresh = true;
     else (void)hipGetLastError();
 }
 static int ba_upload_poses(gsdf_ctx* c) {
-    HIP_TRY(hipMemcpyAsync(c->ba_Rt, c->ba_R.data(), c->ba_R.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->ba_Rt + 9 * (size_t)c->ba_n, c->ba_t.data(), c->ba_t.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->ba.Rt, c->ba_R.data(), c->ba_R.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->ba.Rt + 9 * (size_t)c->ba_n, c->ba_t.data(), c->ba_t.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return GSDF_OK;
 }
@@ -1294,54 +1260,53 @@ int gsdf_ba_setup(gsdf_ctx* c, int n, const float* images_bgr_host, const float*
     int rc = require_frame(c);
     if (rc) return rc;
     if (c->map_type != GSDF_MAP_GRAD) return fail(GSDF_ERR_INVALID, "PhotoBA needs the Gradient-SDF map (a base-sdf context has no gradient)");
-    if (!c->vis) return fail(GSDF_ERR_INVALID, "PhotoBA needs the vis_ bit-vectors: call gsdf_enable_vis before fusing");
+    if (!c->map.vis) return fail(GSDF_ERR_INVALID, "PhotoBA needs the vis_ bit-vectors: call gsdf_enable_vis before fusing");
     if (n <= 0 || n > 64 || !images_bgr_host || !poses16_host || !frame_idx) return fail(GSDF_ERR_INVALID, "bad argument (1..64 keyframes)");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    void* old[] = { c->ba_images, c->ba_Rt, c->ba_frame_idx, c->ba_block_E, c->ba_block_part, c->ba_Hb, c->ba_gate_list, c->ba_gate_tmp, c->counter2, c->ba_mean };
-    for (void* p : old) if (p) (void)hipFree(p);
-    c->ba_gate_list = nullptr; c->ba_gate_tmp = nullptr; c->counter2 = nullptr; c->ba_gate_fresh = false;
-    c->ba_mean = nullptr; c->ba_mean_valid = false;
-    c->ba_images = nullptr; c->ba_Rt = nullptr; c->ba_frame_idx = nullptr; c->ba_block_E = nullptr; c->ba_block_part = nullptr; c->ba_Hb = nullptr;
-    c->ba_n = n; c->ba_reg = reg_weight;
-    const size_t img_bytes = (size_t)n * c->W * c->H * 3 * sizeof(float);
-    HIP_TRY(hipMalloc((void**)&c->ba_images, img_bytes));
-    HIP_TRY(hipMalloc((void**)&c->ba_Rt, (size_t)n * 12 * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&c->ba_frame_idx, (size_t)n * sizeof(int)));
+    c->ba = gsdf_ba_bufs();                                   /* the old setup goes first; until the commit below there is none */
+    c->ba_n = 0; c->ba_gate_fresh = false; c->ba_mean_valid = false;
+    gsdf_ba_bufs b;
+    const size_t img_count = (size_t)n * c->W * c->H * 3;
+    HIP_TRY(b.images.alloc(img_count));
+    HIP_TRY(b.Rt.alloc((size_t)n * 12));
+    HIP_TRY(b.frame_idx.alloc((size_t)n));
     /* two sets of 3 x blocks doubles (energy, voxels, observations per workgroup): gsdf_ba_optimize keeps the sweep behind the
      * pose step and the one behind the distance step apart and reads both with one synchronisation */
-    HIP_TRY(hipMalloc((void**)&c->ba_block_E, (size_t)2 * 3 * gsdf_ba_blocks() * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&c->ba_block_part, (size_t)gsdf_ba_blocks() * n * 27 * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&c->ba_Hb, (size_t)n * 27 * sizeof(float)));
+    HIP_TRY(b.block_E.alloc((size_t)2 * 3 * gsdf_ba_blocks()));
+    HIP_TRY(b.block_part.alloc((size_t)gsdf_ba_blocks() * n * 27));
+    HIP_TRY(b.Hb.alloc((size_t)n * 27));
     {   /* the gate list of the energy / pose sweeps: optional (without it they sweep the whole table) */
-        gsdf_ba_dev d = ba_dev(c);
         size_t bytes = 0;
-        if (gsdf_ba_compact(c->stream, d, nullptr, nullptr, nullptr, &bytes) == hipSuccess &&
-            hipMalloc((void**)&c->ba_gate_list, c->n_slots * sizeof(uint32_t)) == hipSuccess &&
-            hipMalloc(&c->ba_gate_tmp, bytes ? bytes : 8) == hipSuccess && hipMalloc((void**)&c->counter2, sizeof(unsigned long long)) == hipSuccess) {
-            c->ba_gate_tmp_bytes = bytes;
+        if (gsdf_ba_compact(c->stream, ba_dev(c), nullptr, nullptr, nullptr, &bytes) == hipSuccess &&
+            b.gate_list.alloc(c->n_slots) == hipSuccess && b.gate_tmp.alloc(bytes ? bytes : 8) == hipSuccess && b.counter2.alloc(1) == hipSuccess) {
             /* optional on top: 24 B per possible list entry for what the energy sweep hands to the pose sweep (100 MB at 2^22 records) */
             /* GSDF_BA_MEAN_CACHE (read here, so that a test can switch within one context): 0 the pose sweep computes its means
              * itself; 2 (tests only) the stand-alone gsdf_ba_solve_pose trusts that nothing changed since the last energy sweep */
             const char* env = getenv("GSDF_BA_MEAN_CACHE");
             c->ba_mean_on = env ? atoi(env) : 1;
-            if (!c->ba_mean_on || hipMalloc(&c->ba_mean, c->n_slots * 24) != hipSuccess) { (void)hipGetLastError(); c->ba_mean = nullptr; }
+            if (c->ba_mean_on && b.mean.alloc(c->n_slots * 24) != hipSuccess) (void)hipGetLastError();
         } else {
             (void)hipGetLastError();
-            if (c->ba_gate_list) { (void)hipFree(c->ba_gate_list); c->ba_gate_list = nullptr; }
+            b.gate_list.reset(); b.gate_tmp.reset(); b.counter2.reset();
         }
-        c->ba_gate_fresh = false;
     }
-    HIP_TRY(hipMemcpyAsync(c->ba_images, images_bgr_host, img_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->ba_frame_idx, frame_idx, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    c->ba_R.resize(9 * (size_t)n); c->ba_t.resize(3 * (size_t)n);
+    std::vector<float> R(9 * (size_t)n), t(3 * (size_t)n);
     for (int i = 0; i < n; ++i)
         for (int r = 0; r < 3; ++r) {
-            for (int k = 0; k < 3; ++k) c->ba_R[9 * i + 3 * r + k] = poses16_host[16 * i + 4 * r + k];
-            c->ba_t[3 * i + r] = poses16_host[16 * i + 4 * r + 3];
+            for (int k = 0; k < 3; ++k) R[9 * i + 3 * r + k] = poses16_host[16 * i + 4 * r + k];
+            t[3 * i + r] = poses16_host[16 * i + 4 * r + 3];
         }
-    c->ba_mean_valid = false;
-    return ba_upload_poses(c);
+    HIP_TRY(hipMemcpyAsync(b.images, images_bgr_host, img_count * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(b.frame_idx, frame_idx, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(b.Rt, R.data(), R.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(b.Rt + R.size(), t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    /* the commit: only a complete setup, with its keyframe count and poses, reaches the context */
+    c->ba = std::move(b);
+    c->ba_n = n; c->ba_reg = reg_weight;
+    c->ba_R = std::move(R); c->ba_t = std::move(t);
+    return GSDF_OK;
 }
 
 /* the energy sweep enqueued into set `which` of the per-workgroup sums; ba_energy_sum adds a set up in the fixed order */
@@ -1350,7 +1315,7 @@ static int ba_energy_enqueue(gsdf_ctx* c, int which, bool pose_sweep_follows = t
     const gsdf_ba_dev d = ba_dev(c);
     /* the sweep leaves every gated voxel's mean intensity / keyframe set behind for a pose sweep at this same state */
     const bool write_mean = pose_sweep_follows && d.gate_list && d.mean_cache && c->ba_trunc_sq < 0.f;
-    gsdf_launch_ba_energy(c->stream, d, c->ba_block_E + (size_t)which * 3 * gsdf_ba_blocks(), write_mean);
+    gsdf_launch_ba_energy(c->stream, d, c->ba.block_E + (size_t)which * 3 * gsdf_ba_blocks(), write_mean);
     c->ba_mean_valid = write_mean;
     HIP_TRY(hipGetLastError());
     return GSDF_OK;
@@ -1372,7 +1337,7 @@ int gsdf_ba_energy(gsdf_ctx* c, float* E) {
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = ba_energy_enqueue(c, 0))) return rc;
     std::vector<double> h((size_t)3 * gsdf_ba_blocks());
-    HIP_TRY(hipMemcpyAsync(h.data(), c->ba_block_E, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(h.data(), c->ba.block_E, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     *E = ba_energy_sum(c, h.data());
     return GSDF_OK;
@@ -1397,7 +1362,7 @@ int gsdf_ba_solve_dist(gsdf_ctx* c, float damping) {
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     /* the stand-alone entry also counts what the sweep visited (gsdf_ba_counters); gsdf_ba_optimize's sweeps do not */
-    double* cnt = c->ba_block_E + (size_t)3 * gsdf_ba_blocks();
+    double* cnt = c->ba.block_E + (size_t)3 * gsdf_ba_blocks();
     if ((rc = ba_dist_enqueue(c, damping, cnt))) return rc;
     std::vector<double> h((size_t)2 * gsdf_ba_blocks());
     HIP_TRY(hipMemcpyAsync(h.data(), cnt, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -1415,10 +1380,10 @@ static int ba_solve_pose(gsdf_ctx* c, bool wait_upload) {
     const bool list_was_fresh = c->ba_gate_fresh;
     ba_refresh_gate(c);
     /* (the cache belongs to the list the energy sweep walked: a list rebuilt since then has other entries) */
-    gsdf_launch_ba_pose(c->stream, ba_dev(c), c->ba_block_part, c->ba_Hb, c->ba_mean_valid && list_was_fresh);
+    gsdf_launch_ba_pose(c->stream, ba_dev(c), c->ba.block_part, c->ba.Hb, c->ba_mean_valid && list_was_fresh);
     c->ba_mean_valid = false;                                 /* the poses move */
     std::vector<float> hb((size_t)n * 27);
-    HIP_TRY(hipMemcpyAsync(hb.data(), c->ba_Hb, hb.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(hb.data(), c->ba.Hb, hb.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));                 /* the 6x6 systems are solved on the host (:577-589) */
     for (int i = 0; i < n; ++i) {                             /* per-keyframe 6x6 LDLT + pose update (:577-589) */
         const float* v = &hb[27 * (size_t)i];
@@ -1442,8 +1407,8 @@ static int ba_solve_pose(gsdf_ctx* c, bool wait_upload) {
     }
     if (wait_upload) return ba_upload_poses(c);
     /* c->ba_R / ba_t are members: they stay untouched until the caller's next synchronisation, which is behind these copies */
-    HIP_TRY(hipMemcpyAsync(c->ba_Rt, c->ba_R.data(), c->ba_R.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->ba_Rt + 9 * (size_t)c->ba_n, c->ba_t.data(), c->ba_t.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->ba.Rt, c->ba_R.data(), c->ba_R.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->ba.Rt + 9 * (size_t)c->ba_n, c->ba_t.data(), c->ba_t.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
     return GSDF_OK;
 }
 int gsdf_ba_solve_pose(gsdf_ctx* c, float damping) {
@@ -1481,7 +1446,7 @@ int gsdf_ba_optimize(gsdf_ctx* c, int max_it, float* energies, int* n_energies, 
         if ((rc = ba_energy_enqueue(c, 0, false))) return rc;  /* (the distance sweep follows: nobody reads its means) */
         if ((rc = ba_dist_enqueue(c, 1.0f))) return rc;
         if ((rc = ba_energy_enqueue(c, 1))) return rc;
-        HIP_TRY(hipMemcpyAsync(h.data(), c->ba_block_E, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(h.data(), c->ba.block_E, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         E_pose = ba_energy_sum(c, h.data());
         E = ba_energy_sum(c, h.data() + set);
@@ -1507,29 +1472,32 @@ int gsdf_ba_get_poses(gsdf_ctx* c, float* poses16_host) {
     return GSDF_OK;
 }
 
+/* device scratch for a batch of `bytes`: the context's own for single points / small batches (no allocation per call), else
+ * `big`, which lives as long as the caller's frame */
+static int batch_scratch(gsdf_ctx* c, size_t bytes, gsdf_dev<void>& big, void** out) {
+    const bool small = bytes <= GSDF_SCRATCH_BYTES;
+    gsdf_dev<void>& b = small ? c->scratch : big;
+    HIP_TRY(b.grow(small ? GSDF_SCRATCH_BYTES : bytes));
+    *out = b;
+    return GSDF_OK;
+}
+
 int gsdf_query(gsdf_ctx* c, const float* pts_host, int64_t n, float* dist, float* grad, float* w) {
     GSDF_FLUSH(c);
     if (!c || (n > 0 && (!pts_host || !dist || !grad || !w))) return fail(GSDF_ERR_INVALID, "null argument");
     if (n <= 0) return GSDF_OK;
     HIP_TRY(hipSetDevice(c->device));
+    gsdf_dev<void> big;
     float* d = nullptr;
-    const bool small = (size_t)n * 8 * sizeof(float) <= GSDF_SCRATCH_BYTES;       /* single points / small batches: no allocation per call */
-    if (small) {
-        if (!c->scratch) HIP_TRY(hipMalloc(&c->scratch, GSDF_SCRATCH_BYTES));
-        d = (float*)c->scratch;
-    } else HIP_TRY(hipMalloc((void**)&d, (size_t)n * 8 * sizeof(float)));
+    if (int rc = batch_scratch(c, (size_t)n * 8 * sizeof(float), big, (void**)&d)) return rc;
     float *dp = d, *dd = d + 3 * n, *dg = d + 4 * n, *dw = d + 7 * n;
-    hipError_t e = hipMemcpyAsync(dp, pts_host, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        gsdf_launch_query(c->stream, c->tab, c->voxel_size, c->voxel_size_inv, dp, n, dd, dg, dw,
-                          c->map_type == GSDF_MAP_BASE ? c->T : -1.f);
-        e = hipMemcpyAsync(dist, dd, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(grad, dg, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(w, dw, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (!small) (void)hipFree(d);
-    if (e != hipSuccess) return fail(GSDF_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(dp, pts_host, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    gsdf_launch_query(c->stream, c->tab, c->voxel_size, c->voxel_size_inv, dp, n, dd, dg, dw,
+                      c->map_type == GSDF_MAP_BASE ? c->T : -1.f);
+    HIP_TRY(hipMemcpyAsync(dist, dd, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(grad, dg, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(w, dw, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return GSDF_OK;
 }
 
@@ -1538,24 +1506,17 @@ int gsdf_get_voxels(gsdf_ctx* c, const int32_t* keys_host, int64_t n, float* pay
     if (!c || (n > 0 && (!keys_host || !payload || !found))) return fail(GSDF_ERR_INVALID, "null argument");
     if (n <= 0) return GSDF_OK;
     HIP_TRY(hipSetDevice(c->device));
+    gsdf_dev<void> big;
     char* d = nullptr;
-    const bool small = (size_t)n * 36 <= GSDF_SCRATCH_BYTES;
-    if (small) {
-        if (!c->scratch) HIP_TRY(hipMalloc(&c->scratch, GSDF_SCRATCH_BYTES));
-        d = (char*)c->scratch;
-    } else HIP_TRY(hipMalloc((void**)&d, (size_t)n * (3 * sizeof(int32_t) + 5 * sizeof(float) + sizeof(int32_t))));
+    if (int rc = batch_scratch(c, (size_t)n * (3 * sizeof(int32_t) + 5 * sizeof(float) + sizeof(int32_t)), big, (void**)&d)) return rc;
     int32_t* dk = (int32_t*)d;
     float* dp = (float*)(d + (size_t)n * 3 * sizeof(int32_t));
     int32_t* df = (int32_t*)(d + (size_t)n * (3 * sizeof(int32_t) + 5 * sizeof(float)));
-    hipError_t e = hipMemcpyAsync(dk, keys_host, (size_t)n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        gsdf_launch_get_voxels(c->stream, c->tab, dk, n, dp, df);
-        e = hipMemcpyAsync(payload, dp, (size_t)n * 5 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(found, df, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (!small) (void)hipFree(d);
-    if (e != hipSuccess) return fail(GSDF_ERR_HIP, hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(dk, keys_host, (size_t)n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    gsdf_launch_get_voxels(c->stream, c->tab, dk, n, dp, df);
+    HIP_TRY(hipMemcpyAsync(payload, dp, (size_t)n * 5 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(found, df, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return GSDF_OK;
 }
 
@@ -1566,13 +1527,9 @@ static int raycast_enqueue(gsdf_ctx* c, const float K[9], const float R[9], cons
     std::memcpy(pose.t, t, sizeof(pose.t));
     /* per-workgroup counter rows (samples, records): sized for the largest grid seen, kept until reset */
     const size_t n_wg = (size_t)((W + 15) / 16) * (size_t)((H + 15) / 16);
-    if (n_wg > c->rc_rows) {
+    if (n_wg * 8 > c->rc_counts.count()) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->rc_counts) (void)hipFree(c->rc_counts);
-        c->rc_counts = nullptr; c->rc_rows = 0;
-        HIP_TRY(hipMalloc((void**)&c->rc_counts, n_wg * 8 * sizeof(unsigned long long)));
-        HIP_TRY(hipMemsetAsync(c->rc_counts, 0, n_wg * 8 * sizeof(unsigned long long), c->stream));
-        c->rc_rows = n_wg;
+        HIP_TRY(alloc_zeroed(c->rc_counts, n_wg * 8, c->stream));
     }
     if (c->occ_dirty) {                                       /* the map changed since the filters were built */
         gsdf_launch_occ_rebuild(c->stream, c->tab);
@@ -1603,15 +1560,12 @@ int gsdf_raycast(gsdf_ctx* c, const float K[9], const float R[9], const float t[
     if (W <= 0 || H <= 0 || !(zmax > zmin) || !(zmin > 0.f)) return fail(GSDF_ERR_INVALID, "W,H > 0 and 0 < zmin < zmax required");
     HIP_TRY(hipSetDevice(c->device));
     const size_t N = (size_t)W * H;
-    float* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, 4 * N * sizeof(float)));
-    if (int rc = raycast_enqueue(c, K, R, t, W, H, zmin, zmax, d, normals_out ? d + N : nullptr)) { (void)hipFree(d); return rc; }
-    hipError_t e = hipMemcpyAsync(depth_out, d, N * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && normals_out)
-        e = hipMemcpyAsync(normals_out, d + N, 3 * N * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(GSDF_ERR_HIP, hipGetErrorString(e));
+    gsdf_dev<float> d;
+    HIP_TRY(d.alloc(4 * N));
+    if (int rc = raycast_enqueue(c, K, R, t, W, H, zmin, zmax, d, normals_out ? d + N : nullptr)) return rc;
+    HIP_TRY(hipMemcpyAsync(depth_out, d, N * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (normals_out) HIP_TRY(hipMemcpyAsync(normals_out, d + N, 3 * N * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return GSDF_OK;
 }
 
@@ -1620,10 +1574,10 @@ int gsdf_raycast_counters(gsdf_ctx* c, int64_t* samples, int64_t* records, int r
     HIP_TRY(hipSetDevice(c->device));
     unsigned long long tot[4] = { 0, 0, 0, 0 };
     if (c->rc_counts) {
-        std::vector<unsigned long long> h(c->rc_rows * 8);
+        std::vector<unsigned long long> h(c->rc_counts.count());
         HIP_TRY(hipMemcpyAsync(h.data(), c->rc_counts, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        for (size_t i = 0; i < c->rc_rows; ++i) for (int k = 0; k < 4; ++k) tot[k] += h[8 * i + k];
+        for (size_t i = 0; i < h.size() / 8; ++i) for (int k = 0; k < 4; ++k) tot[k] += h[8 * i + k];
         if (reset) HIP_TRY(hipMemsetAsync(c->rc_counts, 0, h.size() * sizeof(unsigned long long), c->stream));
     }
     if (samples) *samples = (int64_t)tot[0];
@@ -1641,46 +1595,43 @@ int gsdf_extract_mesh(gsdf_ctx* c, float iso, const int8_t tri_table[256 * 16], 
     *n_tris = 0;
     /* upper bound of the output: 5 triangles per cube, one cube per voxel; sized by the caller through max_tris */
     const long long cap = max_tris > 0 ? (long long)max_tris : 0;
-    int* d_mn = nullptr; signed char* d_tab = nullptr; float* d_tris = nullptr; unsigned long long* d_keys = nullptr;
-    hipError_t e = hipMalloc((void**)&d_mn, 3 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_tab, 256 * 16);
-    if (e == hipSuccess && cap) e = hipMalloc((void**)&d_tris, (size_t)cap * 9 * sizeof(float));
-    if (e == hipSuccess && cap) e = hipMalloc((void**)&d_keys, (size_t)cap * sizeof(unsigned long long));
+    gsdf_dev<int> d_mn;
+    gsdf_dev<signed char> d_tab;
+    gsdf_dev<float> d_tris;
+    gsdf_dev<unsigned long long> d_keys;
+    HIP_TRY(d_mn.alloc(3));
+    HIP_TRY(d_tab.alloc(256 * 16));
+    if (cap) HIP_TRY(d_tris.alloc((size_t)cap * 9));
+    if (cap) HIP_TRY(d_keys.alloc((size_t)cap));
     const int big[3] = { 2147483647, 2147483647, 2147483647 };
-    if (e == hipSuccess) e = hipMemcpyAsync(d_mn, big, sizeof(big), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tab, tri_table, 256 * 16, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream);
+    HIP_TRY(hipMemcpyAsync(d_mn, big, sizeof(big), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_tab, tri_table, 256 * 16, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream));
     unsigned long long n = 0;
-    if (e == hipSuccess) {
-        gsdf_launch_mesh(c->stream, c->tab, c->n_slots, c->voxel_size, iso, d_mn, d_tab, d_tris, d_keys, c->counter, cap);
-        e = hipMemcpyAsync(&n, c->counter, sizeof(n), hipMemcpyDeviceToHost, c->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    gsdf_launch_mesh(c->stream, c->tab, c->n_slots, c->voxel_size, iso, d_mn, d_tab, d_tris, d_keys, c->counter, cap);
+    HIP_TRY(hipMemcpyAsync(&n, c->counter, sizeof(n), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     const size_t got = (size_t)std::min<unsigned long long>(n, (unsigned long long)cap);
     /* the reference's order (z-y-x sweep, triangles of a cube in table order) = ascending sort key: radix sort of (key, index)
      * on the device, the triangles gathered into that order on the device, ONE copy of the sorted list to the caller */
-    unsigned long long* d_keys2 = nullptr; uint32_t *d_idx = nullptr, *d_idx2 = nullptr; float* d_sorted = nullptr; void* d_tmp = nullptr;
-    if (e == hipSuccess && got && n <= (unsigned long long)cap) {
+    if (got && n <= (unsigned long long)cap) {
+        gsdf_dev<unsigned long long> d_keys2;
+        gsdf_dev<uint32_t> d_idx, d_idx2;
+        gsdf_dev<float> d_sorted;
+        gsdf_dev<void> d_tmp;
         size_t tmp_bytes = 0;
-        e = hipMalloc((void**)&d_keys2, got * sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMalloc((void**)&d_idx, got * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&d_idx2, got * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&d_sorted, got * 9 * sizeof(float));
-        if (e == hipSuccess) e = gsdf_sort_pairs_u64(nullptr, &tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, got, c->stream);
-        if (e == hipSuccess) e = hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 8);
-        if (e == hipSuccess) {
-            gsdf_launch_iota(c->stream, d_idx, got);
-            e = gsdf_sort_pairs_u64(d_tmp, &tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, got, c->stream);
-        }
-        if (e == hipSuccess) {
-            gsdf_launch_gather_tris(c->stream, d_tris, d_idx2, d_sorted, got);
-            e = hipMemcpyAsync(triangles_out, d_sorted, got * 9 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        HIP_TRY(d_keys2.alloc(got));
+        HIP_TRY(d_idx.alloc(got));
+        HIP_TRY(d_idx2.alloc(got));
+        HIP_TRY(d_sorted.alloc(got * 9));
+        HIP_TRY(gsdf_sort_pairs_u64(nullptr, &tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, got, c->stream));
+        HIP_TRY(d_tmp.alloc(tmp_bytes ? tmp_bytes : 8));
+        gsdf_launch_iota(c->stream, d_idx, got);
+        HIP_TRY(gsdf_sort_pairs_u64(d_tmp, &tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, got, c->stream));
+        gsdf_launch_gather_tris(c->stream, d_tris, d_idx2, d_sorted, got);
+        HIP_TRY(hipMemcpyAsync(triangles_out, d_sorted, got * 9 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    (void)hipFree(d_mn); (void)hipFree(d_tab); (void)hipFree(d_tris); (void)hipFree(d_keys);
-    (void)hipFree(d_keys2); (void)hipFree(d_idx); (void)hipFree(d_idx2); (void)hipFree(d_sorted); (void)hipFree(d_tmp);
-    if (e != hipSuccess) return fail(GSDF_ERR_HIP, hipGetErrorString(e));
     *n_tris = (int64_t)n;                                    /* total found, also when it exceeds max_tris */
     if (n > (unsigned long long)cap) return cap ? fail(GSDF_ERR_INVALID, "gsdf_extract_mesh: max_tris too small (n_tris holds the need)") : GSDF_OK;
     return GSDF_OK;

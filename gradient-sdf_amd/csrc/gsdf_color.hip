@@ -201,65 +201,15 @@ __global__ __launch_bounds__(256) void k_cloud_emit(const unsigned long long* __
 
 /* ---- host: gsdf_color_* --------------------------------------------------------------------------------------------------- */
 
-struct gsdf_color_state {
-    /* the snapshot */
-    bool valid = false;
-    long long n = 0, obs = 0;
-    float vs = 0.f;
-    unsigned long long* keys = nullptr; size_t keys_cap = 0;       /* packed (z, y, x)-ordered keys */
-    float* rows = nullptr; size_t rows_cap = 0;                    /* GSDF_COLOR_ROW floats per key */
-    long long cloud_n = -1;                                         /* the cloud of the snapshot, made on first request */
-    float* cloud = nullptr; size_t cloud_cap = 0;
-    /* scratch of the compute */
-    float* images = nullptr; size_t images_cap = 0;
-    float* Rt = nullptr; size_t Rt_cap = 0;
-    int* fidx = nullptr; size_t fidx_cap = 0;
-    uint32_t* list = nullptr; size_t list_cap = 0;
-    uint32_t* slots = nullptr; size_t slots_cap = 0;
-    unsigned long long* keys_in = nullptr; size_t keys_in_cap = 0;
-    uint32_t* counts = nullptr; size_t counts_cap = 0;
-    uint32_t* offsets = nullptr; size_t offsets_cap = 0;
-    unsigned char* tmp = nullptr; size_t tmp_cap = 0;              /* rocPRIM scratch */
-    unsigned long long* words = nullptr; size_t words_cap = 0;      /* [0] selected voxels, [1] observations */
-};
-
-namespace {
-
-int cfail(int code, const std::string& msg) { return gsdf_fail(code, msg); }
-
-/* device buffers grow and are kept (a compute per BA run, at sizes that change little) */
-template <class T>
-int color_grow(T** p, size_t* cap, size_t count) {
-    if (count <= *cap && *p) return GSDF_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    const size_t want = std::max<size_t>(count, 1);
-    HIP_TRY(hipMalloc((void**)p, want * sizeof(T)));
-    *cap = want;
-    return GSDF_OK;
-}
-#define COLOR_GROW(field, count) do { const int rc_ = color_grow(&S->field, &S->field##_cap, (count)); if (rc_) return rc_; } while (0)
-
-}  // namespace
-
-void gsdf_color_release(gsdf_ctx* c) {
-    gsdf_color_state* S = c->color;
-    if (!S) return;
-    void* ptrs[] = { S->keys, S->rows, S->cloud, S->images, S->Rt, S->fidx, S->list, S->slots, S->keys_in, S->counts, S->offsets, S->tmp, S->words };
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    delete S;
-    c->color = nullptr;
-}
-void gsdf_color_drop(gsdf_ctx* c) {
-    if (c->color) { c->color->valid = false; c->color->n = 0; c->color->obs = 0; c->color->cloud_n = -1; }
-}
+static int cfail(int code, const std::string& msg) { return gsdf_fail(code, msg); }
 
 int gsdf_color_compute(gsdf_ctx* c, int n, const float* images_bgr_host, const float* poses16_host, const int* frame_idx,
                        int64_t* n_voxels) {
     if (!c) return cfail(GSDF_ERR_INVALID, "null context");
     if (int rc = gsdf_flush_pending(c)) return rc;
-    if (!c->planes) return cfail(GSDF_ERR_INVALID, "gsdf_normals_init must be called first (image size and intrinsics)");
+    if (!c->frame.planes) return cfail(GSDF_ERR_INVALID, "gsdf_normals_init must be called first (image size and intrinsics)");
     if (c->map_type != GSDF_MAP_GRAD) return cfail(GSDF_ERR_INVALID, "ColorUpsampler needs the Gradient-SDF map (a base-sdf context has no gradient)");
-    if (!c->vis) return cfail(GSDF_ERR_INVALID, "ColorUpsampler needs the vis_ bit-vectors: call gsdf_enable_vis before fusing");
+    if (!c->map.vis) return cfail(GSDF_ERR_INVALID, "ColorUpsampler needs the vis_ bit-vectors: call gsdf_enable_vis before fusing");
     if (n < 1 || n > 64) return cfail(GSDF_ERR_INVALID, "bad argument (1..64 keyframes)");
     const bool from_ba = !images_bgr_host || !poses16_host || !frame_idx;
     if (from_ba && !c->ba_n) return cfail(GSDF_ERR_INVALID, "NULL images, poses or frame_idx name PhotoBA's: gsdf_ba_setup was not called");
@@ -269,7 +219,7 @@ int gsdf_color_compute(gsdf_ctx* c, int n, const float* images_bgr_host, const f
     /* poses and keyframe ids on the host first: the ids are checked, the poses split into R (row-major) and t */
     std::vector<int> fid((size_t)n);
     if (frame_idx) std::copy(frame_idx, frame_idx + n, fid.begin());
-    else HIP_TRY(hipMemcpy(fid.data(), c->ba_frame_idx, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    else HIP_TRY(hipMemcpy(fid.data(), c->ba.frame_idx, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
     for (int v : fid)
         if (v < 0) return cfail(GSDF_ERR_INVALID, "frame_idx: keyframe ids must be >= 0");
     std::vector<float> Rt((size_t)n * 12);
@@ -279,19 +229,18 @@ int gsdf_color_compute(gsdf_ctx* c, int n, const float* images_bgr_host, const f
                 Rt[9 * (size_t)i + 3 * r + k] = poses16_host ? poses16_host[16 * (size_t)i + 4 * r + k] : c->ba_R[9 * (size_t)i + 3 * r + k];
             Rt[9 * (size_t)n + 3 * (size_t)i + r] = poses16_host ? poses16_host[16 * (size_t)i + 4 * r + 3] : c->ba_t[3 * (size_t)i + r];
         }
-    if (!c->color) c->color = new gsdf_color_state();
-    gsdf_color_state* S = c->color;
+    gsdf_color_state* S = &c->color;
     S->valid = false; S->cloud_n = -1;
-    COLOR_GROW(Rt, Rt.size());
-    COLOR_GROW(fidx, (size_t)n);
-    COLOR_GROW(words, 2);
-    COLOR_GROW(list, c->n_slots);
+    HIP_TRY(S->Rt.grow(Rt.size()));
+    HIP_TRY(S->fidx.grow((size_t)n));
+    HIP_TRY(S->words.grow(2));
+    HIP_TRY(S->list.grow(c->n_slots));
     HIP_TRY(hipMemcpyAsync(S->Rt, Rt.data(), Rt.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(S->fidx, fid.data(), fid.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    const float* images = c->ba_images;                                          /* NULL: gsdf_ba_setup's, no second upload */
+    const float* images = c->ba.images;                                          /* NULL: gsdf_ba_setup's, no second upload */
     if (images_bgr_host) {
         const size_t cnt = (size_t)n * c->W * c->H * 3;
-        COLOR_GROW(images, cnt);
+        HIP_TRY(S->images.grow(cnt));
         HIP_TRY(hipMemcpyAsync(S->images, images_bgr_host, cnt * sizeof(float), hipMemcpyHostToDevice, c->stream));
         images = S->images;
     }
@@ -300,28 +249,28 @@ int gsdf_color_compute(gsdf_ctx* c, int n, const float* images_bgr_host, const f
     const float gate = (float)(std::sqrt(3.) * c->voxel_size);                   /* init :143 */
     const color_sel_pred pred{ c->tab.bkeys, c->tab.vox, gate };
     size_t bytes = 0;
-    HIP_TRY(rocprim::select(nullptr, bytes, rocprim::counting_iterator<uint32_t>(0u), S->list, S->words, c->n_slots, pred, c->stream));
-    COLOR_GROW(tmp, bytes);
-    bytes = S->tmp_cap;
-    HIP_TRY(rocprim::select(S->tmp, bytes, rocprim::counting_iterator<uint32_t>(0u), S->list, S->words, c->n_slots, pred, c->stream));
+    HIP_TRY(rocprim::select(nullptr, bytes, rocprim::counting_iterator<uint32_t>(0u), S->list.get(), S->words.get(), c->n_slots, pred, c->stream));
+    HIP_TRY(S->tmp.grow(bytes));
+    bytes = S->tmp.bytes();
+    HIP_TRY(rocprim::select(S->tmp, bytes, rocprim::counting_iterator<uint32_t>(0u), S->list.get(), S->words.get(), c->n_slots, pred, c->stream));
     unsigned long long N = 0;
     HIP_TRY(hipMemcpyAsync(&N, S->words, sizeof(N), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     /* order: (z, y, x) keys of the selection sorted together with their slots */
-    COLOR_GROW(keys_in, (size_t)N);
-    COLOR_GROW(keys, (size_t)N);
-    COLOR_GROW(slots, (size_t)N);
-    COLOR_GROW(rows, (size_t)N * GSDF_COLOR_ROW);
+    HIP_TRY(S->keys_in.grow((size_t)N));
+    HIP_TRY(S->keys.grow((size_t)N));
+    HIP_TRY(S->slots.grow((size_t)N));
+    HIP_TRY(S->rows.grow((size_t)N * GSDF_COLOR_ROW));
     if (N) {
         hipLaunchKernelGGL(k_color_keys, dim3((unsigned int)((N + 255) / 256)), dim3(256), 0, c->stream, S->list, c->tab.bkeys, S->keys_in, (size_t)N);
         bytes = 0;
         HIP_TRY(gsdf_sort_pairs_u64(nullptr, &bytes, S->keys_in, S->keys, S->list, S->slots, (size_t)N, c->stream));
-        COLOR_GROW(tmp, bytes);
-        bytes = S->tmp_cap;
+        HIP_TRY(S->tmp.grow(bytes));
+        bytes = S->tmp.bytes();
         HIP_TRY(gsdf_sort_pairs_u64(S->tmp, &bytes, S->keys_in, S->keys, S->list, S->slots, (size_t)N, c->stream));
         color_args a;
         a.tab = c->tab; a.slots = S->slots; a.n_vox = (long long)N;
-        a.vis = c->vis; a.vis_words = c->vis_words;
+        a.vis = c->map.vis; a.vis_words = c->vis_words;
         a.n = n; a.W = c->W; a.H = c->H;
         a.images = images; a.R = S->Rt; a.t = S->Rt + 9 * (size_t)n; a.frame_idx = S->fidx;
         a.fx = c->K[0]; a.fy = c->K[4]; a.cx = c->K[2]; a.cy = c->K[5]; a.vs = c->voxel_size;
@@ -340,15 +289,15 @@ int gsdf_color_compute(gsdf_ctx* c, int n, const float* images_bgr_host, const f
 
 int gsdf_color_counters(gsdf_ctx* c, int64_t* voxels, int64_t* observations) {
     if (!c || !voxels || !observations) return cfail(GSDF_ERR_INVALID, "null argument");
-    if (!c->color || !c->color->valid) return cfail(GSDF_ERR_INVALID, "gsdf_color_compute was not called (or the map was reset)");
-    *voxels = c->color->n; *observations = c->color->obs;
+    if (!c->color.valid) return cfail(GSDF_ERR_INVALID, "gsdf_color_compute was not called (or the map was reset)");
+    *voxels = c->color.n; *observations = c->color.obs;
     return GSDF_OK;
 }
 
 int gsdf_color_export(gsdf_ctx* c, int32_t* keys, float* rows, int64_t max_n, int64_t* n) {
     if (!c) return cfail(GSDF_ERR_INVALID, "null context");
-    if (!c->color || !c->color->valid) return cfail(GSDF_ERR_INVALID, "gsdf_color_compute was not called (or the map was reset)");
-    const gsdf_color_state* S = c->color;
+    if (!c->color.valid) return cfail(GSDF_ERR_INVALID, "gsdf_color_compute was not called (or the map was reset)");
+    const gsdf_color_state* S = &c->color;
     if (n) *n = S->n;
     if (S->n == 0 || max_n <= 0 || (!keys && !rows)) return GSDF_OK;
     if (max_n < S->n) return cfail(GSDF_ERR_INVALID, "export buffer too small");
@@ -368,29 +317,29 @@ int gsdf_color_export(gsdf_ctx* c, int32_t* keys, float* rows, int64_t max_n, in
 
 int gsdf_color_cloud(gsdf_ctx* c, float* rows9, int64_t max_n, int64_t* n) {
     if (!c) return cfail(GSDF_ERR_INVALID, "null context");
-    if (!c->color || !c->color->valid) return cfail(GSDF_ERR_INVALID, "gsdf_color_compute was not called (or the map was reset)");
-    gsdf_color_state* S = c->color;
+    if (!c->color.valid) return cfail(GSDF_ERR_INVALID, "gsdf_color_compute was not called (or the map was reset)");
+    gsdf_color_state* S = &c->color;
     HIP_TRY(hipSetDevice(c->device));
     if (S->cloud_n < 0) {                                                      /* predicate, prefix sum, compaction */
         const size_t N = (size_t)S->n;
         const float vs4 = (float)(.25 * S->vs);                                /* extractCloud :254 */
         unsigned long long total = 0;
         if (N) {
-            COLOR_GROW(counts, N);
-            COLOR_GROW(offsets, N);
+            HIP_TRY(S->counts.grow(N));
+            HIP_TRY(S->offsets.grow(N));
             const dim3 grid((unsigned int)((N + 255) / 256));
             hipLaunchKernelGGL(k_cloud_count, grid, dim3(256), 0, c->stream, S->rows, N, vs4, S->counts);
             size_t bytes = 0;
-            HIP_TRY(rocprim::exclusive_scan(nullptr, bytes, S->counts, S->offsets, 0u, N, rocprim::plus<uint32_t>(), c->stream));
-            COLOR_GROW(tmp, bytes);
-            bytes = S->tmp_cap;
-            HIP_TRY(rocprim::exclusive_scan(S->tmp, bytes, S->counts, S->offsets, 0u, N, rocprim::plus<uint32_t>(), c->stream));
+            HIP_TRY(rocprim::exclusive_scan(nullptr, bytes, S->counts.get(), S->offsets.get(), 0u, N, rocprim::plus<uint32_t>(), c->stream));
+            HIP_TRY(S->tmp.grow(bytes));
+            bytes = S->tmp.bytes();
+            HIP_TRY(rocprim::exclusive_scan(S->tmp, bytes, S->counts.get(), S->offsets.get(), 0u, N, rocprim::plus<uint32_t>(), c->stream));
             uint32_t last[2] = { 0u, 0u };
             HIP_TRY(hipMemcpyAsync(&last[0], S->offsets + N - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipMemcpyAsync(&last[1], S->counts + N - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));
             total = (unsigned long long)last[0] + last[1];
-            COLOR_GROW(cloud, (size_t)total * 9);
+            HIP_TRY(S->cloud.grow((size_t)total * 9));
             hipLaunchKernelGGL(k_cloud_emit, grid, dim3(256), 0, c->stream, S->keys, S->rows, N, S->vs, vs4, S->offsets, S->cloud);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(c->stream));

@@ -1,14 +1,16 @@
 /*
- * gsdf_ctx.h -- the context behind the C-ABI handle (private to libgsdf.so: gsdf_capi.hip, gsdf_merge.hip).
+ * gsdf_ctx.h -- the context behind the C-ABI handle (private to libgsdf.so: gsdf_capi.hip, gsdf_merge.hip, gsdf_color.hip).
  */
 #ifndef GSDF_CTX_H_
 #define GSDF_CTX_H_
 
 #include "../../include/gsdf.h"
+#include "gsdf_dev.h"
 #include "gsdf_kernels.h"
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <deque>
 #include <string>
@@ -26,9 +28,6 @@ struct gsdf_ctx;
 int gsdf_flush_pending(gsdf_ctx* c);               /* gsdf_capi.hip: launch the deferred GT-pose fusion, if one waits */
 int gsdf_grow_impl(gsdf_ctx* c, int new_capacity_log2);      /* gsdf_merge.hip: rehash into a larger table */
 void gsdf_enqueue_block_count(gsdf_ctx* c, unsigned int tag);   /* gsdf_merge.hip: existing blocks | tag << 32 -> pinned words progress[4..5] */
-struct gsdf_color_state;                           /* gsdf_color.hip: the ColorUpsampler snapshot and its scratch */
-void gsdf_color_release(gsdf_ctx* c);              /* frees it (gsdf_destroy) */
-void gsdf_color_drop(gsdf_ctx* c);                 /* forgets the snapshot, keeps the buffers (gsdf_reset) */
 
 inline int gsdf_fail(int code, const std::string& msg) {
     g_gsdf_err = msg;
@@ -119,6 +118,76 @@ struct gsdf_lookahead {
     }
 };
 
+/* The context's device memory, one struct per lifetime.  Each is built in a local and moved into the context once its last
+ * allocation succeeded, so the context holds a whole group or an empty one -- never half of one. */
+
+/* the table (gsdf_create, gsdf_grow); gsdf_ctx::tab is the POD view of it the kernels take by value */
+struct gsdf_map_bufs {
+    gsdf_dev<gsdf_payload> vox;
+    gsdf_dev<unsigned long long> bkeys;
+    gsdf_dev<uint32_t> occ;                        /* block filter (64 bits per block entry), then the cell filter (1 bit per block entry, at least one word) */
+    gsdf_dev<uint32_t> vis;                        /* optional vis_ bit-vectors, n_slots x vis_words (gsdf_enable_vis) */
+    hipError_t alloc(size_t n_slots, size_t vis_words) {
+        hipError_t e;
+        if ((e = vox.alloc(n_slots)) != hipSuccess || (e = bkeys.alloc(n_slots / GSDF_BLOCK_VOX)) != hipSuccess ||
+            (e = occ.alloc(n_slots / 32 + std::max<size_t>(n_slots / GSDF_BLOCK_VOX / 32, 1))) != hipSuccess) return e;
+        return vis_words ? vis.alloc(n_slots * vis_words) : hipSuccess;
+    }
+    gsdf_table table(size_t n_slots) const { return gsdf_table{ bkeys, vox, (uint32_t)(n_slots / GSDF_BLOCK_VOX - 1), occ }; }
+};
+
+/* normal estimator, frame scratch and tracker rows: everything gsdf_normals_init allocates (planes != nullptr: there is a frame) */
+struct gsdf_frame_bufs {
+    gsdf_dev<float> planes;                        /* 11 planes */
+    gsdf_dev<float> depth_stage;                   /* H2D staging for host-pointer entry points */
+    gsdf_dev<float> normals;                       /* 3 sets of 3 planes */
+    gsdf_dev<uint32_t> tile_stats;                 /* per set: [fuse_blocks][4] statistics of the frame's fusion tiles (gsdf_kernels.hip: gsdf_tile_stats) */
+    gsdf_dev<double> partials;                     /* 3 rotating buffers of tracker partial sums */
+    gsdf_dev<void> track_rows;                     /* k_track_all: the workgroups' rows of sums, two buffers (pass parity) */
+    gsdf_dev<unsigned int> track_abort;            /* k_track_all: abort word */
+    gsdf_dev<unsigned long long> blk_counters;
+    gsdf_dev<unsigned int> tile_flags;             /* per-tile hand-off flags of k_fuse */
+    gsdf_dev<uint32_t> tile_order;                 /* launch order of the fusion tiles (gsdf_fuse_tile_order) */
+    gsdf_dev<gsdf_deferred> deferred;
+    gsdf_dev<unsigned int> deferred_count;
+    gsdf_dev<unsigned int> fuse_ticket;            /* arrivals of finished k_fuse workgroups (reset by the last one) */
+    gsdf_dev<float> frame_log;
+    gsdf_dev<float> depth_sampled;                 /* the compacted pixels of gsdf_track_sampled (sampling > 1), lazily allocated */
+};
+
+/* PhotoBA: everything gsdf_ba_setup allocates.  gate_list, gate_tmp, counter2 and mean are optional (the sweeps use the whole table) */
+struct gsdf_ba_bufs {
+    gsdf_dev<float> images;
+    gsdf_dev<float> Rt;                            /* n x 9 rotations then n x 3 translations */
+    gsdf_dev<int> frame_idx;
+    gsdf_dev<double> block_E;
+    gsdf_dev<float> block_part;
+    gsdf_dev<float> Hb;
+    gsdf_dev<uint32_t> gate_list;                  /* slots of the voxels with |dist| <= voxel size (the gate of getEnergy / solvePose), slot order */
+    gsdf_dev<void> gate_tmp;                       /* rocPRIM select scratch */
+    gsdf_dev<unsigned long long> counter2;         /* device word: entries of gate_list */
+    gsdf_dev<void> mean;                           /* per entry of gate_list: what the last energy sweep's first loop found (24 B each; gsdf_ba_dev::mean_cache) */
+};
+
+/* ColorUpsampler (gsdf_color.hip): the snapshot and the scratch of its compute; the buffers grow and are kept */
+struct gsdf_color_state {
+    bool valid = false;
+    long long n = 0, obs = 0;
+    float vs = 0.f;
+    gsdf_dev<unsigned long long> keys;             /* packed (z, y, x)-ordered keys */
+    gsdf_dev<float> rows;                          /* GSDF_COLOR_ROW floats per key */
+    long long cloud_n = -1;                        /* the cloud of the snapshot, made on first request */
+    gsdf_dev<float> cloud;
+    /* scratch of the compute */
+    gsdf_dev<float> images, Rt;
+    gsdf_dev<int> fidx;
+    gsdf_dev<uint32_t> list, slots, counts, offsets;
+    gsdf_dev<unsigned long long> keys_in;
+    gsdf_dev<void> tmp;                            /* rocPRIM scratch */
+    gsdf_dev<unsigned long long> words;            /* [0] selected voxels, [1] observations */
+    void drop() { valid = false; n = 0; obs = 0; cloud_n = -1; }   /* forgets the snapshot, keeps the buffers (gsdf_reset) */
+};
+
 struct gsdf_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -133,39 +202,25 @@ struct gsdf_ctx {
     /* table */
     int capacity_log2 = 0;
     size_t n_slots = 0;
-    gsdf_table tab{ nullptr, nullptr, 0, nullptr };
+    gsdf_map_bufs map;
+    gsdf_table tab{ nullptr, nullptr, 0, nullptr };  /* = map.table(n_slots) */
     /* normal estimator + frame scratch */
     int W = 0, H = 0, win = 0;
     float K[9] = { 0 };
-    float* planes = nullptr;                       /* 11 planes */
-    float* depth_stage = nullptr;                  /* H2D staging for host-pointer entry points */
-    float* normals = nullptr;                      /* 3 sets of 3 planes */
-    uint32_t* tile_stats = nullptr;                /* per set: [fuse_blocks][4] statistics of the frame's fusion tiles (gsdf_kernels.hip: gsdf_tile_stats) */
+    gsdf_frame_bufs frame;
     /* tracker */
-    gsdf_dev_state* st = nullptr;
-    double* partials = nullptr;                    /* 3 rotating buffers of tracker partial sums */
+    gsdf_dev<gsdf_dev_state> st;
     unsigned int track_rot = 0;                    /* tracker launches issued so far, mod 3 (selects the sum buffers) */
     int track_blocks = 0;
-    void* track_rows = nullptr;                    /* k_track_all: the workgroups' rows of sums, two buffers (pass parity) */
-    unsigned int* track_abort = nullptr;           /* k_track_all: abort word */
     int persist = 0;                               /* optimize() as one launch (k_track_all) instead of one launch per pass */
-    unsigned long long* blk_counters = nullptr;
     int fuse_blocks = 0;                           /* tiles of a frame */
-    gsdf_deferred* deferred = nullptr;
-    unsigned int* deferred_count = nullptr;
-    unsigned int* fuse_ticket = nullptr;           /* arrivals of finished k_fuse workgroups (reset by the last one) */
     unsigned int deferred_cap = 0;
     unsigned int fuse_tag = 0;                     /* serial of the last fusion launch */
-    unsigned int* tile_flags = nullptr;            /* per-tile hand-off flags of k_fuse */
-    uint32_t* tile_order = nullptr;                /* launch order of the fusion tiles (gsdf_fuse_tile_order) */
-    uint32_t* vis = nullptr;                       /* optional vis_ bit-vectors, n_slots x vis_words */
-    int vis_words = 0;
-    unsigned long long* rc_counts = nullptr;       /* raycaster: per-workgroup rows of (samples, records, fast / slow iterations of wave 0) */
-    size_t rc_rows = 0;
+    int vis_words = 0;                             /* words per voxel of map.vis */
+    gsdf_dev<unsigned long long> rc_counts;        /* raycaster: per-workgroup rows of 8 (samples, records, fast / slow iterations of wave 0) */
     long long rc_iters[2] = { 0, 0 };              /* loop iterations of the workgroups' wave 0 as of the last gsdf_raycast_counters */
     bool fuse_head = true;                         /* the frame's first fusion launch performs the head of the first batch's last tracker launch (GSDF_FUSE_HEAD) */
-    float* depth_sampled = nullptr;                /* the compacted pixels of gsdf_track_sampled (sampling > 1), lazily allocated */
-    void* scratch = nullptr;                       /* device scratch of gsdf_query / gsdf_get_voxels for small batches (GSDF_SCRATCH_BYTES) */
+    gsdf_dev<void> scratch;                        /* device scratch of gsdf_query / gsdf_get_voxels for small batches (GSDF_SCRATCH_BYTES) */
     bool occ_dirty = false;                        /* blocks may have been inserted since the raycaster's filters (gsdf_table::occ) were built */
     /* the reference's map grows without bound (MapGradPixelSdf.h:65-68); here: gsdf_grow, or by itself when gsdf_set_auto_grow
      * named a limit -- every few fusions the number of existing blocks is counted into a pinned word, and a frame entry that
@@ -179,33 +234,22 @@ struct gsdf_ctx {
     bool grow_forget = false;                      /* set by gsdf_grow / gsdf_reset: restart the bookkeeping above */
     int grow_max_lag = GSDF_GROW_MAX_LAG_DEFAULT;
     long long grow_syncs = 0;                      /* entries that had to wait for an exact count (statistics for the tests) */
-    unsigned int* grow_scratch = nullptr;          /* two device words of k_count_blocks */
+    gsdf_dev<unsigned int> grow_scratch;           /* two device words of k_count_blocks */
     bool merged = false;                           /* gsdf_merge_allreduce has run: the map is the sum of all ranks (one-shot) */
-    struct mx_buf { void* p = nullptr; size_t bytes = 0; } mx[GSDF_MX_BUFS];   /* scratch of the exchange (gsdf_merge.hip): grows, never shrinks */
+    gsdf_dev<void> mx[GSDF_MX_BUFS];               /* scratch of the exchange (gsdf_merge.hip): grows, never shrinks */
     /* PhotoBA (PhotometricOptimizer) */
     int ba_n = 0;
     float ba_reg = 10.f;
     float ba_trunc_sq = -1.f;                      /* OptSettings::lambda_sq when loss == TRUNC_L2, else < 0 */
-    float* ba_images = nullptr;
-    float* ba_Rt = nullptr;                        /* device: n x 9 rotations then n x 3 translations */
-    int* ba_frame_idx = nullptr;
-    double* ba_block_E = nullptr;
-    float* ba_block_part = nullptr;
-    float* ba_Hb = nullptr;
+    gsdf_ba_bufs ba;
     std::vector<float> ba_R, ba_t;                 /* host copies of the keyframe poses being optimised */
-    uint32_t* ba_gate_list = nullptr;              /* slots of the voxels with |dist| <= voxel size (the gate of getEnergy / solvePose), slot order */
-    void* ba_gate_tmp = nullptr;                   /* rocPRIM select scratch */
-    size_t ba_gate_tmp_bytes = 0;
-    unsigned long long* counter2 = nullptr;        /* device word: entries of ba_gate_list */
-    bool ba_gate_fresh = false;                    /* the list matches the distances in the table */
-    void* ba_mean = nullptr;                       /* per entry of ba_gate_list: what the last energy sweep's first loop found (24 B each; gsdf_ba_dev::mean_cache) */
+    bool ba_gate_fresh = false;                    /* ba.gate_list matches the distances in the table */
     int ba_mean_on = 1;                            /* GSDF_BA_MEAN_CACHE (read by gsdf_ba_setup) */
     bool ba_mean_valid = false;                    /* ... at the very state (poses, distances, gate list) the next pose sweep will see */
     long long ba_last_voxels = 0, ba_last_obs = 0; /* what the last energy sweep read back counted (gsdf_ba_counters) */
-    gsdf_color_state* color = nullptr;             /* ColorUpsampler (gsdf_color_compute): created on first use */
+    gsdf_color_state color;                        /* ColorUpsampler (gsdf_color_compute) */
     unsigned int track_serial = 0;                 /* optimize() call counter */
-    volatile unsigned int* progress = nullptr;     /* pinned host words written by the tracker epilogue */
-    unsigned int* progress_dev = nullptr;
+    gsdf_pinned<unsigned int> progress;            /* 16 pinned host words written by the tracker epilogue, the fusion and the block count */
     int adaptive = 1;                              /* issue tracker passes in batches, following the device (see enqueue_track) */
     int far_table = -1;                            /* fusion kernel's LDS table: -1 chosen per launch from the previous fusions, 0 / 1 pinned */
     long long fuse_launches = 0, far_table_launches = 0; /* fusion launches since create/reset, and those with the larger table (gsdf_get_stats) */
@@ -213,12 +257,11 @@ struct gsdf_ctx {
                                                       more is most likely one that runs all 25 (pass counts on the bench stream: 142 x <= 6, 7 x 7..22,
                                                       51 x 25) -- batches of 8 behind the first: 6 656 -> 6 815 frames/s on the default window (4 / 12 / 21: 6 656 / 6 780 / 6 760) */
     int lazy_fuse = 1;                             /* the frame's fusion is queued behind the first and the last batch of passes only; in between once optimize() has ended */
-    unsigned long long* trace = nullptr;           /* test build: per-workgroup time stamps of k_fuse (gsdf_debug_flags & 64) */
+    gsdf_dev<unsigned long long> trace;            /* test build: per-workgroup time stamps of k_fuse (gsdf_debug_flags & 64) */
     int debug = 0;                                 /* path-forcing / measurement switches (gsdf_debug_flags; test build only) */
-    float* frame_log = nullptr;
     long long frame_log_cap = 0;
     /* misc */
-    unsigned long long* counter = nullptr;
+    gsdf_dev<unsigned long long> counter;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool profiling = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events[GSDF_PROF_SLOTS];
@@ -246,6 +289,7 @@ struct gsdf_ctx {
     gsdf_ncache ncache() const {
         const size_t N = (size_t)W * H;
         gsdf_ncache nc;
+        const float* planes = frame.planes;
         nc.x0 = planes; nc.y0 = planes + N; nc.x0n = planes + 2 * N; nc.y0n = planes + 3 * N;
         nc.ninv = planes + 4 * N; nc.q11 = planes + 5 * N; nc.q12 = planes + 6 * N; nc.q13 = planes + 7 * N;
         nc.q22 = planes + 8 * N; nc.q23 = planes + 9 * N; nc.q33 = planes + 10 * N;

@@ -151,12 +151,19 @@ struct host_transport : transport {
 enum { MX_HDR = 0, MX_AGREE, MX_KEYS_ALL, MX_SORTED, MX_UNION, MX_TMP, MX_DENSE, MX_VIS, MX_COUNT_ };
 static_assert(MX_COUNT_ <= GSDF_MX_BUFS, "gsdf_ctx::mx is too small");
 int mx_ensure(gsdf_ctx* c, int i, size_t bytes, bool spare) {
-    if (c->mx[i].bytes >= bytes && c->mx[i].p) return GSDF_OK;
-    if (c->mx[i].p) { (void)hipFree(c->mx[i].p); c->mx[i].p = nullptr; c->mx[i].bytes = 0; }      /* no exchange is in flight: every one ends with a sync */
-    const size_t want = std::max<size_t>(spare ? bytes + bytes / 4 : bytes, 256);
-    HIP_TRY(hipMalloc(&c->mx[i].p, want));
-    c->mx[i].bytes = want;
+    if (c->mx[i] && c->mx[i].bytes() >= bytes) return GSDF_OK;
+    /* (a buffer that is replaced: no exchange is in flight, every one ends with a sync) */
+    HIP_TRY(c->mx[i].alloc(std::max<size_t>(spare ? bytes + bytes / 4 : bytes, 256)));
     return GSDF_OK;
+}
+/* the scratch whose size follows from (ranks, capacity) alone: the gathered keys, their sorted and unique forms, rocPRIM's */
+int mx_ensure_sized(gsdf_ctx* c, size_t n_all) {
+    for (int i : { MX_KEYS_ALL, MX_SORTED, MX_UNION })
+        if (int rc = mx_ensure(c, i, n_all * sizeof(unsigned long long), false)) return rc;
+    size_t tmp_sort = 0, tmp_uniq = 0;
+    HIP_TRY(gsdf_sort_keys_u64(nullptr, &tmp_sort, nullptr, nullptr, n_all, c->stream));
+    HIP_TRY(gsdf_unique_u64(nullptr, &tmp_uniq, nullptr, nullptr, nullptr, n_all, c->stream));
+    return mx_ensure(c, MX_TMP, std::max(tmp_sort, tmp_uniq), false);
 }
 
 int read_status(gsdf_ctx* c) {
@@ -199,7 +206,7 @@ __global__ void k_union_size(const unsigned long long* uni, unsigned long long* 
 /* agreement point: every rank reports whether its buffers for the next stage exist */
 int agree(gsdf_ctx* c, transport& tr, int local_rc, const char* what) {
     const int R = tr.nranks;
-    long long* scratch_dev = (long long*)c->mx[MX_AGREE].p;          /* R + 1 words */
+    long long* scratch_dev = c->mx[MX_AGREE].as<long long>();          /* R + 1 words */
     const long long mine = local_rc;
     HIP_TRY(hipMemcpyAsync(scratch_dev + R, &mine, sizeof(mine), hipMemcpyHostToDevice, c->stream));
     int rc = tr.allgather(c, scratch_dev + R, scratch_dev, sizeof(long long));
@@ -240,23 +247,14 @@ int merge_impl(gsdf_ctx* c, transport& tr, int64_t* n_blocks_out, int64_t* bytes
     if (int rc = mx_ensure(c, MX_AGREE, (size_t)(R + 1) * sizeof(long long), false)) return rc;
     /* 1. everything whose size follows from (ranks, capacity) alone is prepared BEFORE the header goes out: a failure travels
      *    in the header */
-    size_t tmp_sort = 0, tmp_uniq = 0;
-    auto prepare = [&]() -> int {
-        if (int rc = mx_ensure(c, MX_KEYS_ALL, n_all * sizeof(unsigned long long), false)) return rc;
-        if (int rc = mx_ensure(c, MX_SORTED, n_all * sizeof(unsigned long long), false)) return rc;
-        if (int rc = mx_ensure(c, MX_UNION, n_all * sizeof(unsigned long long), false)) return rc;
-        HIP_TRY(gsdf_sort_keys_u64(nullptr, &tmp_sort, nullptr, nullptr, n_all, c->stream));
-        HIP_TRY(gsdf_unique_u64(nullptr, &tmp_uniq, nullptr, nullptr, nullptr, n_all, c->stream));
-        return mx_ensure(c, MX_TMP, std::max(tmp_sort, tmp_uniq), false);
-    };
-    const int prep = prepare();
-    const int vw_mine = c->vis ? c->vis_words : 0;
+    const int prep = mx_ensure_sized(c, n_all);
+    const int vw_mine = c->map.vis ? c->vis_words : 0;
     auto dense_capacity = [&]() -> long long {      /* blocks the pack buffers hold as they are */
-        long long b = c->mx[MX_DENSE].p ? (long long)(c->mx[MX_DENSE].bytes / (GSDF_BLOCK_VOX * 5 * sizeof(float))) : 0;
-        if (vw_mine) b = std::min(b, c->mx[MX_VIS].p ? (long long)(c->mx[MX_VIS].bytes / (GSDF_BLOCK_VOX * (size_t)vw_mine * sizeof(uint32_t))) : 0ll);
+        long long b = c->mx[MX_DENSE] ? (long long)(c->mx[MX_DENSE].bytes() / (GSDF_BLOCK_VOX * 5 * sizeof(float))) : 0;
+        if (vw_mine) b = std::min(b, c->mx[MX_VIS] ? (long long)(c->mx[MX_VIS].bytes() / (GSDF_BLOCK_VOX * (size_t)vw_mine * sizeof(uint32_t))) : 0ll);
         return b;
     };
-    merge_hdr* hd = (merge_hdr*)c->mx[MX_HDR].p;
+    merge_hdr* hd = c->mx[MX_HDR].as<merge_hdr>();
     merge_hdr mine;
     std::memset(&mine, 0, sizeof(mine));
     mine.cap_blocks = (long long)cap; mine.vis_words = vw_mine; mine.err = prep; mine.token = random_token(c);
@@ -306,21 +304,21 @@ int merge_impl(gsdf_ctx* c, transport& tr, int64_t* n_blocks_out, int64_t* bytes
         if (!grc) {
             cap = c->n_slots / GSDF_BLOCK_VOX;
             n_all = cap * (size_t)R;
-            grc = prepare();
+            grc = mx_ensure_sized(c, n_all);
         }
         rc = agree(c, tr, grc, "grow its table to the largest rank's capacity");
         if (rc) return rc;
     }
     /* 2. the ranks' key arrays -> sorted union, on the device */
-    unsigned long long* keys_all = (unsigned long long*)c->mx[MX_KEYS_ALL].p;
-    unsigned long long* sorted = (unsigned long long*)c->mx[MX_SORTED].p;
-    unsigned long long* uk = (unsigned long long*)c->mx[MX_UNION].p;
+    unsigned long long* keys_all = c->mx[MX_KEYS_ALL].as<unsigned long long>();
+    unsigned long long* sorted = c->mx[MX_SORTED].as<unsigned long long>();
+    unsigned long long* uk = c->mx[MX_UNION].as<unsigned long long>();
     rc = tr.allgather(c, c->tab.bkeys, keys_all, cap * sizeof(unsigned long long));
     if (rc) return rc;
-    size_t tmp_bytes = c->mx[MX_TMP].bytes;
-    HIP_TRY(gsdf_sort_keys_u64(c->mx[MX_TMP].p, &tmp_bytes, keys_all, sorted, n_all, c->stream));
-    tmp_bytes = c->mx[MX_TMP].bytes;
-    HIP_TRY(gsdf_unique_u64(c->mx[MX_TMP].p, &tmp_bytes, sorted, uk, c->counter, n_all, c->stream));
+    size_t tmp_bytes = c->mx[MX_TMP].bytes();
+    HIP_TRY(gsdf_sort_keys_u64(c->mx[MX_TMP], &tmp_bytes, keys_all, sorted, n_all, c->stream));
+    tmp_bytes = c->mx[MX_TMP].bytes();
+    HIP_TRY(gsdf_unique_u64(c->mx[MX_TMP], &tmp_bytes, sorted, uk, c->counter, n_all, c->stream));
     hipLaunchKernelGGL(k_union_size, dim3(1), dim3(64), 0, c->stream, uk, c->counter);
     HIP_TRY(hipGetLastError());
     unsigned long long nu64 = 0;
@@ -342,10 +340,10 @@ int merge_impl(gsdf_ctx* c, transport& tr, int64_t* n_blocks_out, int64_t* bytes
         if (rc) return rc;
     }
     if (nu) {
-        float* dense = (float*)c->mx[MX_DENSE].p;
-        uint32_t* dense_vis = (uint32_t*)c->mx[MX_VIS].p;
+        float* dense = c->mx[MX_DENSE].as<float>();
+        uint32_t* dense_vis = c->mx[MX_VIS].as<uint32_t>();
         gsdf_launch_pack_blocks(c->stream, c->tab, uk, (long long)nu, dense);
-        if (vw) gsdf_launch_pack_vis(c->stream, c->tab, c->vis, vw, frames_before, uk, (long long)nu, dense_vis);
+        if (vw) gsdf_launch_pack_vis(c->stream, c->tab, c->map.vis, vw, frames_before, uk, (long long)nu, dense_vis);
         HIP_TRY(hipGetLastError());
         rc = tr.allreduce_sum_f32(c, dense, nu * GSDF_BLOCK_VOX * 5);
         if (rc) return rc;
@@ -355,7 +353,7 @@ int merge_impl(gsdf_ctx* c, transport& tr, int64_t* n_blocks_out, int64_t* bytes
         }
         c->occ_dirty = true;
         gsdf_launch_unpack_blocks(c->stream, c->tab, uk, (long long)nu, dense, c->st);
-        if (vw) gsdf_launch_unpack_vis(c->stream, c->tab, c->vis, vw, uk, (long long)nu, dense_vis);
+        if (vw) gsdf_launch_unpack_vis(c->stream, c->tab, c->map.vis, vw, uk, (long long)nu, dense_vis);
     }
     /* Sdf::counter_ of the merged map: the frames of all ranks (frame f of rank r is integrated frame frames_before(r) + f) */
     gsdf_launch_set_frames(c->stream, c->st, frames_total);
@@ -456,10 +454,10 @@ __global__ __launch_bounds__(256) void k_count_blocks_dev(const unsigned long lo
 }
 
 void gsdf_enqueue_block_count(gsdf_ctx* c, unsigned int tag) {
-    if (!c->progress_dev || !c->grow_scratch) return;
+    if (!c->progress.dev() || !c->grow_scratch) return;
     const size_t cap = c->n_slots / GSDF_BLOCK_VOX;
     hipLaunchKernelGGL(k_count_blocks, dim3(64), dim3(256), 0, c->stream, c->tab.bkeys, cap, c->grow_scratch,
-                       reinterpret_cast<unsigned long long*>(c->progress_dev + 4), tag);
+                       reinterpret_cast<unsigned long long*>(c->progress.dev() + 4), tag);
     (void)hipGetLastError();
 }
 
@@ -471,27 +469,20 @@ int gsdf_grow_impl(gsdf_ctx* c, int new_capacity_log2) {
     if (int rc = gsdf_flush_pending(c)) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     const size_t n_new = (size_t)1 << new_capacity_log2;
-    gsdf_table nt{ nullptr, nullptr, 0, nullptr };
-    uint32_t* nvis = nullptr;
-    auto release = [&]() { if (nt.vox) (void)hipFree(nt.vox); if (nt.bkeys) (void)hipFree(nt.bkeys); if (nt.occ) (void)hipFree(nt.occ); if (nvis) (void)hipFree(nvis); };
-    hipError_t e;
-    if ((e = hipMalloc((void**)&nt.vox, n_new * sizeof(gsdf_payload))) != hipSuccess ||
-        (e = hipMalloc((void**)&nt.bkeys, (n_new / GSDF_BLOCK_VOX) * sizeof(unsigned long long))) != hipSuccess ||
-        (e = hipMalloc((void**)&nt.occ, n_new / 8 + std::max<size_t>(n_new / GSDF_BLOCK_VOX / 8, 4))) != hipSuccess ||
-        (c->vis && (e = hipMalloc((void**)&nvis, n_new * (size_t)c->vis_words * sizeof(uint32_t))) != hipSuccess)) {
-        release();
+    const int vw = c->map.vis ? c->vis_words : 0;
+    gsdf_map_bufs nm;                                          /* the new table: released on every return but the last */
+    hipError_t e = nm.alloc(n_new, (size_t)vw);
+    if (e != hipSuccess) {
         (void)hipGetLastError();
         return gsdf_fail(GSDF_ERR_HIP, std::string("gsdf_grow: ") + hipGetErrorString(e));      /* the map is untouched */
     }
-    nt.block_mask = (uint32_t)(n_new / GSDF_BLOCK_VOX - 1);
+    const gsdf_table nt = nm.table(n_new);
     /* A sticky GSDF_STATUS_TABLE_FULL from an earlier fusion must not stop the map from growing: the rehash into an
      * empty, larger table reports its own failure through the same bit, so the bit is looked at before and after.  (The old
-     * error stays sticky -- samples WERE dropped -- and gsdf_sync keeps reporting it until gsdf_reset.)  Every failure path
-     * below releases the new table. */
+     * error stays sticky -- samples WERE dropped -- and gsdf_sync keeps reporting it until gsdf_reset.) */
     gsdf_dev_state s0, s1;
     auto bail = [&](hipError_t err, const char* what) {
-        (void)hipStreamSynchronize(c->stream);                 /* nothing may still write into the buffers that are freed */
-        release();
+        (void)hipStreamSynchronize(c->stream);                 /* nothing may still write into the new table, which goes with `nm` */
         (void)hipGetLastError();
         return gsdf_fail(GSDF_ERR_HIP, std::string("gsdf_grow: ") + what + ": " + hipGetErrorString(err));
     };
@@ -502,10 +493,9 @@ int gsdf_grow_impl(gsdf_ctx* c, int new_capacity_log2) {
         if ((e = hipMemcpy(&c->st->status, &cleared, sizeof(int), hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "clearing the status");
     }
     gsdf_launch_table_clear(c->stream, nt, n_new);
-    if (nvis && (e = hipMemsetAsync(nvis, 0, n_new * (size_t)c->vis_words * sizeof(uint32_t), c->stream)) != hipSuccess) return bail(e, "clearing vis_");
+    if (vw && (e = hipMemsetAsync(nm.vis, 0, nm.vis.bytes(), c->stream)) != hipSuccess) return bail(e, "clearing vis_");
     const size_t nb_old = c->n_slots / GSDF_BLOCK_VOX;
-    hipLaunchKernelGGL(k_rehash, dim3((unsigned int)((nb_old + 3) / 4)), dim3(256), 0, c->stream, c->tab, nt, c->vis, nvis, c->vis ? c->vis_words : 0,
-                       nb_old, c->st);
+    hipLaunchKernelGGL(k_rehash, dim3((unsigned int)((nb_old + 3) / 4)), dim3(256), 0, c->stream, c->tab, nt, c->map.vis, nm.vis, vw, nb_old, c->st);
     if ((e = hipGetLastError()) != hipSuccess) return bail(e, "launching the rehash");
     if ((e = hipMemcpyAsync(&s1, c->st, sizeof(s1), hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return bail(e, "reading the status");
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return bail(e, "the rehash");
@@ -513,25 +503,19 @@ int gsdf_grow_impl(gsdf_ctx* c, int new_capacity_log2) {
         const int restored = s1.status | GSDF_STATUS_TABLE_FULL;
         (void)hipMemcpy(&c->st->status, &restored, sizeof(int), hipMemcpyHostToDevice);
     }
-    if (s1.status & GSDF_STATUS_TABLE_FULL) {                  /* cannot happen: the new table is empty and larger */
-        release();
-        return gsdf_fail(GSDF_ERR_TABLE_FULL, "gsdf_grow: the rehash ran out of probes");
-    }
-    (void)hipFree(c->tab.vox); (void)hipFree(c->tab.bkeys); (void)hipFree(c->tab.occ);
-    if (c->vis) (void)hipFree(c->vis);
-    c->tab = nt; c->vis = nvis;
+    /* (cannot happen: the new table is empty and larger) */
+    if (s1.status & GSDF_STATUS_TABLE_FULL) return gsdf_fail(GSDF_ERR_TABLE_FULL, "gsdf_grow: the rehash ran out of probes");
+    c->map = std::move(nm);                                    /* the old table is released here */
+    c->tab = nt;
     c->n_slots = n_new; c->capacity_log2 = new_capacity_log2;
     c->occ_dirty = true;                                       /* the raycaster's filters are rebuilt from the keys when it next runs */
     /* PhotoBA's gate list was sized for the old table: the sweeps fall back to the whole table until the next gsdf_ba_setup */
-    if (c->ba_gate_list) { (void)hipFree(c->ba_gate_list); c->ba_gate_list = nullptr; }
-    if (c->ba_mean) { (void)hipFree(c->ba_mean); c->ba_mean = nullptr; }
+    c->ba.gate_list.reset();
+    c->ba.mean.reset();
     c->ba_gate_fresh = false; c->ba_mean_valid = false;
     c->grow_forget = true;                                     /* auto-grow: the counts in flight describe the old table */
     return GSDF_OK;
 }
-
-namespace {
-} // namespace
 
 extern "C" {
 
@@ -578,7 +562,7 @@ int gsdf_merge_from(gsdf_ctx* dst, gsdf_ctx* src) {
     if (dst->device != src->device) return gsdf_fail(GSDF_ERR_INVALID, "gsdf_merge_from: the contexts live on different devices (use gsdf_merge_allreduce between devices)");
     if (dst->voxel_size != src->voxel_size || dst->T != src->T) return gsdf_fail(GSDF_ERR_INVALID, "gsdf_merge_from: voxel size / truncation differ");
     if (dst->map_type != src->map_type) return gsdf_fail(GSDF_ERR_INVALID, "gsdf_merge_from: the contexts have different map types");
-    if ((dst->vis != nullptr) != (src->vis != nullptr) || (dst->vis && dst->vis_words != src->vis_words))
+    if ((dst->map.vis != nullptr) != (src->map.vis != nullptr) || (dst->map.vis && dst->vis_words != src->vis_words))
         return gsdf_fail(GSDF_ERR_INVALID, "gsdf_merge_from: gsdf_enable_vis must have been called alike on both contexts");
     HIP_TRY(hipSetDevice(dst->device));
     if (int rc = gsdf_flush_pending(src)) return rc;
@@ -612,8 +596,8 @@ int gsdf_merge_from(gsdf_ctx* dst, gsdf_ctx* src) {
             return gsdf_fail(GSDF_ERR_TABLE_FULL, "gsdf_merge_from: dst cannot hold the blocks of both maps (" + std::to_string(n_dst) + " + " +
                              std::to_string(n_src) + " of " + std::to_string(dst->n_slots / GSDF_BLOCK_VOX) + " entries); dst is unchanged -- gsdf_grow it or allow it with gsdf_set_auto_grow");
     }
-    hipLaunchKernelGGL(k_merge_from, dim3((unsigned int)((nb_src + 3) / 4)), dim3(256), 0, dst->stream, src->tab, dst->tab, src->vis, dst->vis,
-                       dst->vis ? dst->vis_words : 0, (long long)ds.frames, nb_src, dst->st);
+    hipLaunchKernelGGL(k_merge_from, dim3((unsigned int)((nb_src + 3) / 4)), dim3(256), 0, dst->stream, src->tab, dst->tab, src->map.vis, dst->map.vis,
+                       dst->map.vis ? dst->vis_words : 0, (long long)ds.frames, nb_src, dst->st);
     HIP_TRY(hipGetLastError());
     dst->occ_dirty = true;
     dst->ba_gate_fresh = false;
@@ -638,28 +622,22 @@ int gsdf_merge_prepare(gsdf_ctx* c, int nranks) {
     const size_t cap = c->n_slots / GSDF_BLOCK_VOX, n_all = cap * (size_t)nranks;
     if (int rc = mx_ensure(c, MX_HDR, (size_t)(nranks + 1) * sizeof(merge_hdr), false)) return rc;
     if (int rc = mx_ensure(c, MX_AGREE, (size_t)(nranks + 1) * sizeof(long long), false)) return rc;
-    if (int rc = mx_ensure(c, MX_KEYS_ALL, n_all * sizeof(unsigned long long), false)) return rc;
-    if (int rc = mx_ensure(c, MX_SORTED, n_all * sizeof(unsigned long long), false)) return rc;
-    if (int rc = mx_ensure(c, MX_UNION, n_all * sizeof(unsigned long long), false)) return rc;
-    size_t tmp_sort = 0, tmp_uniq = 0;
-    HIP_TRY(gsdf_sort_keys_u64(nullptr, &tmp_sort, nullptr, nullptr, n_all, c->stream));
-    HIP_TRY(gsdf_unique_u64(nullptr, &tmp_uniq, nullptr, nullptr, nullptr, n_all, c->stream));
-    if (int rc = mx_ensure(c, MX_TMP, std::max(tmp_sort, tmp_uniq), false)) return rc;
+    if (int rc = mx_ensure_sized(c, n_all)) return rc;
     /* one run on this map's own keys (the other ranks' parts of the buffer: empty entries) */
-    unsigned long long* keys_all = (unsigned long long*)c->mx[MX_KEYS_ALL].p;
+    unsigned long long* keys_all = c->mx[MX_KEYS_ALL].as<unsigned long long>();
     HIP_TRY(hipMemsetAsync(keys_all, 0xFF, n_all * sizeof(unsigned long long), c->stream));
     HIP_TRY(hipMemcpyAsync(keys_all, c->tab.bkeys, cap * sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
-    size_t tb = c->mx[MX_TMP].bytes;
-    HIP_TRY(gsdf_sort_keys_u64(c->mx[MX_TMP].p, &tb, keys_all, (unsigned long long*)c->mx[MX_SORTED].p, n_all, c->stream));
-    tb = c->mx[MX_TMP].bytes;
-    HIP_TRY(gsdf_unique_u64(c->mx[MX_TMP].p, &tb, (unsigned long long*)c->mx[MX_SORTED].p, (unsigned long long*)c->mx[MX_UNION].p, c->counter, n_all, c->stream));
-    hipLaunchKernelGGL(k_union_size, dim3(1), dim3(64), 0, c->stream, (unsigned long long*)c->mx[MX_UNION].p, c->counter);
+    size_t tb = c->mx[MX_TMP].bytes();
+    HIP_TRY(gsdf_sort_keys_u64(c->mx[MX_TMP], &tb, keys_all, c->mx[MX_SORTED].as<unsigned long long>(), n_all, c->stream));
+    tb = c->mx[MX_TMP].bytes();
+    HIP_TRY(gsdf_unique_u64(c->mx[MX_TMP], &tb, c->mx[MX_SORTED].as<unsigned long long>(), c->mx[MX_UNION].as<unsigned long long>(), c->counter, n_all, c->stream));
+    hipLaunchKernelGGL(k_union_size, dim3(1), dim3(64), 0, c->stream, c->mx[MX_UNION].as<unsigned long long>(), c->counter);
     unsigned long long n_mine = 0;
     HIP_TRY(hipMemcpyAsync(&n_mine, c->counter, sizeof(n_mine), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const size_t guess = std::min<size_t>(cap, std::max<size_t>(2 * (size_t)n_mine, 1024));
     if (int rc = mx_ensure(c, MX_DENSE, guess * GSDF_BLOCK_VOX * 5 * sizeof(float), false)) return rc;
-    if (c->vis) if (int rc = mx_ensure(c, MX_VIS, guess * GSDF_BLOCK_VOX * (size_t)c->vis_words * sizeof(uint32_t), false)) return rc;
+    if (c->map.vis) if (int rc = mx_ensure(c, MX_VIS, guess * GSDF_BLOCK_VOX * (size_t)c->vis_words * sizeof(uint32_t), false)) return rc;
     return GSDF_OK;
 }
 
