@@ -138,6 +138,7 @@ def load(path=None):
         "gsdf_color_export": (C.c_int, [vp, i32p, fp, C.c_int64, i64p]),
         "gsdf_color_cloud": (C.c_int, [vp, fp, C.c_int64, i64p]),
         "gsdf_color_counters": (C.c_int, [vp, i64p, i64p]),
+        "gsdf_color_mesh": (C.c_int, [vp, C.c_float, fp, C.POINTER(C.c_uint8), C.c_int64, i64p]),
         "gsdf_merge_prepare": (C.c_int, [vp, C.c_int]),
         "gsdf_grow": (C.c_int, [vp, C.c_int]),
         "gsdf_set_auto_grow": (C.c_int, [vp, C.c_int]),
@@ -198,7 +199,7 @@ ABI_SYMBOLS = [
     "gsdf_track", "gsdf_track_sampled", "gsdf_hint_next_depth_dev", "gsdf_track_and_fuse_ahead_dev", "gsdf_set_pose", "gsdf_get_pose", "gsdf_track_and_fuse_dev", "gsdf_read_frame_log",
     "gsdf_sync", "gsdf_get_stats", "gsdf_count", "gsdf_export", "gsdf_enable_vis", "gsdf_export_vis",
     "gsdf_ba_setup", "gsdf_ba_set_loss", "gsdf_ba_energy", "gsdf_ba_solve_pose", "gsdf_ba_solve_dist", "gsdf_ba_optimize", "gsdf_ba_get_poses", "gsdf_ba_counters",
-    "gsdf_color_compute", "gsdf_color_export", "gsdf_color_cloud", "gsdf_color_counters", "gsdf_grow", "gsdf_set_auto_grow", "gsdf_capacity", "gsdf_merge_from", "gsdf_create_shards", "gsdf_merge_prepare",
+    "gsdf_color_compute", "gsdf_color_export", "gsdf_color_cloud", "gsdf_color_counters", "gsdf_color_mesh", "gsdf_grow", "gsdf_set_auto_grow", "gsdf_capacity", "gsdf_merge_from", "gsdf_create_shards", "gsdf_merge_prepare",
     "gsdf_merge_raw", "gsdf_export_raw_dev",
     "gsdf_merge_raw_dev", "gsdf_block_keys_dev", "gsdf_pack_blocks_dev", "gsdf_unpack_blocks_dev",
     "gsdf_merge_allreduce", "gsdf_merge_allreduce_with", "gsdf_rccl_unique_id", "gsdf_rccl_comm_init", "gsdf_rccl_comm_count",
@@ -558,6 +559,17 @@ class GradSdf:
         a, b = C.c_int64(0), C.c_int64(0)
         self._chk(self.L.gsdf_color_counters(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def color_mesh(self, iso=0.0):
+        """gsdf_color_mesh (ColorUpsampler::extractMesh): (tris float32 [n, 3, 3], rgb uint8 [n, 3, 3]) of the colour snapshot's
+        sub-voxel grid, in the reference's sweep order"""
+        n = C.c_int64(0)
+        self._chk(self.L.gsdf_color_mesh(self.h, C.c_float(iso), None, None, 0, C.byref(n)))
+        tris = np.empty((n.value, 3, 3), np.float32)
+        rgb = np.empty((n.value, 3, 3), np.uint8)
+        if n.value:
+            self._chk(self.L.gsdf_color_mesh(self.h, C.c_float(iso), _fp(tris), rgb.ctypes.data_as(C.POINTER(C.c_uint8)), n.value, C.byref(n)))
+        return tris, rgb
 
     def merge_raw(self, keys, payload_raw):
         k = np.ascontiguousarray(keys, np.int32).reshape(-1, 3)

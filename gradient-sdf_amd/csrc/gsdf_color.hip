@@ -6,6 +6,8 @@
  *   order       --                    packed (z, y, x) keys of the selection, radix-sorted with their slots (gsdf_sort.hip)
  *   k_color     computeColor :334-377 8 lanes per Hr voxel (SdfVoxelHr, SdfVoxel.h:83-101), one per sub-voxel
  *   k_cloud_*   extractCloud :251-330 per-voxel predicate and count, exclusive scan, compaction into 9-float rows
+ *   k_hr_mesh   extractMesh :240-249  HrLayeredMarchingCubes::computeIsoSurface (mesh/HrLayeredMarchingCubes.cpp:359-822): 8 lanes
+ *                                     per Hr voxel, one fine cube each; neighbours by binary search in the sorted keys
  *
  * The result is a snapshot, like the reference's SdfHrMap copy: it lives in buffers of its own, sorted by key, and later
  * fusion, BA steps or table growth leave it as it is until the next gsdf_color_compute.  The table is only read.
@@ -21,8 +23,11 @@
 #include <rocprim/iterator/counting_iterator.hpp>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <vector>
+
+#include "../../include/gsdf_mc_tables.h"
 
 #define GSDF_COLOR_ROW 37            /* dist, weight, grad[3], d[8], r[8], g[8], b[8] */
 
@@ -350,5 +355,222 @@ int gsdf_color_cloud(gsdf_ctx* c, float* rows9, int64_t max_n, int64_t* n) {
     if (S->cloud_n == 0 || max_n <= 0 || !rows9) return GSDF_OK;
     if (max_n < S->cloud_n) return cfail(GSDF_ERR_INVALID, "cloud buffer too small");
     HIP_TRY(hipMemcpy(rows9, S->cloud, (size_t)S->cloud_n * 9 * sizeof(float), hipMemcpyDeviceToHost));
+    return GSDF_OK;
+}
+
+/* ---- extractMesh: HrLayeredMarchingCubes::computeIsoSurface (mesh/HrLayeredMarchingCubes.cpp:359-822) over the snapshot -------- */
+
+#define GSDF_HR_KEY_BITS 20          /* bits per fine coordinate of the sweep key: 3 x 20 + 3 for the triangle number */
+
+/* bounding box over ALL snapshot keys (:374-381): box[0..2] = minimum (preset to INT_MAX), box[3..5] = maximum (INT_MIN) */
+__global__ __launch_bounds__(256) void k_hr_bbox(const unsigned long long* __restrict__ keys, size_t n, int* box) {
+    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t stride = (size_t)gridDim.x * 256;
+    int m[6] = { INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN };
+    for (; i < n; i += stride) {
+        int p[3];
+        gsdf_key_unpack(keys[i], &p[0], &p[1], &p[2]);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { m[a] = p[a] < m[a] ? p[a] : m[a]; m[3 + a] = p[a] > m[3 + a] ? p[a] : m[3 + a]; }
+    }
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        int v = m[a];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const int other = __shfl_xor(v, o); v = (a < 3 ? other < v : other > v) ? other : v; }
+        if ((threadIdx.x & 63) == 0) { if (a < 3) atomicMin(&box[a], v); else atomicMax(&box[a], v); }
+    }
+}
+
+/* corner c of a cube -> dx | dy << 1 | dz << 2, the numbering of computeLutIndex (:680-687) -- k_mesh's CORNER table:
+ * (1,1,0) (1,0,0) (0,0,0) (0,1,0), then the same with dz = 1 */
+__device__ __forceinline__ int hr_corner_bits(int c) { return ((0x2013 >> (4 * (c & 3))) & 3) | ((c >> 2) << 2); }
+/* setVoxel :666-668 and getColor :771: static_cast<unsigned char>(float); a NaN (a voxel no keyframe counted) is undefined
+ * behaviour in the reference and 0 here */
+__device__ __forceinline__ unsigned int hr_byte(float v) { return isnan(v) ? 0u : ((unsigned int)(int)v & 0xffu); }
+
+struct hr_mesh_args {
+    const unsigned long long* keys;   /* the snapshot: packed keys in (z, y, x) order ... */
+    const float* rows;                /* ... and their GSDF_COLOR_ROW floats */
+    long long n;
+    int mn[3], mx[3];                 /* bounding box of the keys */
+    float vs, iso;
+    const signed char* tri_table;
+    float* tris;                      /* 9 floats per triangle */
+    uint32_t* cols;                   /* 3 words per triangle: r | g << 8 | b << 16 per vertex */
+    unsigned long long* skeys;        /* sweep key per triangle */
+    unsigned long long* counter;
+    long long max_tris;
+};
+
+/* 8 lanes per Hr voxel as in k_color: lane (i & 7) anchors the fine cube whose (0,0,0) corner is sub-voxel i, i.e. fine cell
+ * 2 (X - min) + bit per axis (copyCube :638-653).  The cube's other corners lie in this voxel and in up to 7 coarse neighbours
+ * (+x, +y, +z): lane j of the group looks for neighbour (j & 1, j >> 1 & 1, j >> 2) by binary search in the sorted keys -- all of
+ * them sort after the voxel itself -- and leaves its row index in LDS for the group.  A missing neighbour is zeroWeights
+ * (:611-628).  The sweep (:410-417) stops at dim - 2 = 2 extent - 2 per axis: no cube is anchored in a voxel of the box's maximal
+ * coarse layer.  Triangles are appended with the sweep key (fine z, y, x, triangle number); the host sorts them. */
+__global__ __launch_bounds__(256) void k_hr_mesh(hr_mesh_args a) {
+    __shared__ int s_nb[256];                                                  /* per group: row index of neighbour j, -1 = missing */
+    __shared__ int s_row[8][256];                                              /* per lane: row index of cube corner c ... */
+    __shared__ float s_d[8][256];                                              /* ... and its distance */
+    const int tid = threadIdx.x, sub = tid & 7, g0 = tid & ~7;
+    const long long item = ((long long)blockIdx.x * 256 + tid) >> 3;
+    const bool live = item < a.n;
+    int x = 0, y = 0, z = 0, nb = -1;
+    if (live) {
+        gsdf_key_unpack(a.keys[item], &x, &y, &z);
+        const int nx = x + (sub & 1), ny = y + ((sub >> 1) & 1), nz = z + (sub >> 2);
+        if (sub == 0) nb = (int)item;
+        else if (gsdf_key_in_range(nx, ny, nz)) {
+            const unsigned long long want = gsdf_key_pack(nx, ny, nz);
+            long long lo = item + 1, hi = a.n;
+            while (lo < hi) {
+                const long long mid = lo + ((hi - lo) >> 1);
+                if (a.keys[mid] < want) lo = mid + 1; else hi = mid;
+            }
+            if (lo < a.n && a.keys[lo] == want) nb = (int)lo;
+        }
+    }
+    s_nb[tid] = nb;
+    __syncthreads();
+    if (!live || x >= a.mx[0] || y >= a.mx[1] || z >= a.mx[2]) return;         /* the sweep's dim - 2 bounds (:410-417) */
+    /* computeLutIndex :675-720 */
+    bool ok = true;
+    int idx = 0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const int cb = hr_corner_bits(c);
+        const int r = s_nb[g0 + (sub & cb)];                                   /* the coarse voxel steps where bit and offset are both 1 */
+        float w = 0.f, d = 0.f;
+        if (r >= 0) { const float* row = a.rows + (size_t)r * GSDF_COLOR_ROW; w = row[1]; d = row[5 + (sub ^ cb)]; }
+        if (w == 0.0f) ok = false;
+        if (d > a.iso) idx |= 1 << c;
+        s_row[c][tid] = r;
+        s_d[c][tid] = d;
+    }
+    if (!ok || idx == 0 || idx == 255) return;
+    const int f0 = 2 * (x - a.mn[0]) + (sub & 1), f1 = 2 * (y - a.mn[1]) + ((sub >> 1) & 1), f2 = 2 * (z - a.mn[2]) + (sub >> 2);
+    const float o0 = -(float)a.mn[0] * a.vs, o1 = -(float)a.mn[1] * a.vs, o2 = -(float)a.mn[2] * a.vs;     /* origin_ :384 */
+    const signed char* t = a.tri_table + 16 * idx;
+    for (int k = 0; k < 15 && t[k] >= 0; k += 3) {
+        gsdf_v3 p[3];
+        uint32_t col[3];
+#pragma unroll
+        for (int v = 0; v < 3; ++v) {
+            /* edge e -> its corners in getVertex order (:422-576): k_mesh's EDGE table */
+            const int e = t[k + v];
+            const int ca = e < 8 ? e : e - 8, cb = e < 8 ? (e & 4) | ((e + 1) & 3) : e - 4;
+            /* voxelToWorld :817-821: 0.5f * ((float)i * vs) - origin */
+            const int ba = hr_corner_bits(ca), bb = hr_corner_bits(cb);
+            const gsdf_v3 wa = { 0.5f * ((float)(f0 + (ba & 1)) * a.vs) - o0, 0.5f * ((float)(f1 + ((ba >> 1) & 1)) * a.vs) - o1,
+                                 0.5f * ((float)(f2 + (ba >> 2)) * a.vs) - o2 };
+            const gsdf_v3 wb = { 0.5f * ((float)(f0 + (bb & 1)) * a.vs) - o0, 0.5f * ((float)(f1 + ((bb >> 1) & 1)) * a.vs) - o1,
+                                 0.5f * ((float)(f2 + (bb >> 2)) * a.vs) - o2 };
+            p[v] = mesh_interpolate(s_d[ca][tid], s_d[cb][tid], wa, wb, a.iso);
+            /* getColor :756-773 with the endpoints in the order of ITS calls: reversed for edges 2, 3, 6, 7 (:458, :471, :510,
+             * :523).  Red, green and blue are read at the cell's own index (the reference reads green at idx + 1 and blue at
+             * idx + 2, other cells of its layer window: not a function of the map). */
+            const bool rev = e < 8 && (e & 2);
+            const int c1 = rev ? cb : ca, c2 = rev ? ca : cb;
+            const float* r1 = a.rows + (size_t)s_row[c1][tid] * GSDF_COLOR_ROW + 13 + (sub ^ hr_corner_bits(c1));
+            const float* r2 = a.rows + (size_t)s_row[c2][tid] * GSDF_COLOR_ROW + 13 + (sub ^ hr_corner_bits(c2));
+            const gsdf_v3 q1 = { (float)hr_byte(r1[0] * 255.f) / 255.f, (float)hr_byte(r1[8] * 255.f) / 255.f, (float)hr_byte(r1[16] * 255.f) / 255.f };
+            const gsdf_v3 q2 = { (float)hr_byte(r2[0] * 255.f) / 255.f, (float)hr_byte(r2[8] * 255.f) / 255.f, (float)hr_byte(r2[16] * 255.f) / 255.f };
+            const gsdf_v3 cv = mesh_interpolate(s_d[c1][tid], s_d[c2][tid], q1, q2, a.iso);
+            col[v] = hr_byte(cv.x * 255.f) | (hr_byte(cv.y * 255.f) << 8) | (hr_byte(cv.z * 255.f) << 16);
+        }
+        auto same = [](const gsdf_v3& u, const gsdf_v3& w) { return u.x == w.x && u.y == w.y && u.z == w.z; };
+        if (same(p[0], p[1]) || same(p[0], p[2]) || same(p[1], p[2])) continue;          /* computeTriangles :789 */
+        const unsigned long long o = atomicAdd(a.counter, 1ull);
+        if ((long long)o >= a.max_tris) continue;
+        float* out = a.tris + 9 * o;
+#pragma unroll
+        for (int v = 0; v < 3; ++v) { out[3 * v] = p[v].x; out[3 * v + 1] = p[v].y; out[3 * v + 2] = p[v].z; a.cols[3 * o + v] = col[v]; }
+        a.skeys[o] = ((((unsigned long long)(uint32_t)f2 << (2 * GSDF_HR_KEY_BITS)) | ((unsigned long long)(uint32_t)f1 << GSDF_HR_KEY_BITS) |
+                       (unsigned long long)(uint32_t)f0) << 3) | (unsigned long long)(k / 3);
+    }
+}
+
+/* out[9 t + 3 v + ch] = byte ch of cols[3 order[t] + v]: one lane per byte */
+__global__ __launch_bounds__(256) void k_hr_gather_cols(const uint32_t* __restrict__ cols, const uint32_t* __restrict__ order,
+                                                         uint8_t* __restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n * 9) return;
+    const size_t t = i / 9, k = i - t * 9;
+    out[i] = (uint8_t)(cols[(size_t)order[t] * 3 + k / 3] >> (8 * (k % 3)));
+}
+
+int gsdf_color_mesh(gsdf_ctx* c, float iso, float* triangles_out, uint8_t* colors_out, int64_t max_tris, int64_t* n_tris) {
+    if (!c) return cfail(GSDF_ERR_INVALID, "null context");
+    if (!c->color.valid) return cfail(GSDF_ERR_INVALID, "gsdf_color_compute was not called (or the map was reset)");
+    if (!n_tris || (max_tris > 0 && !triangles_out)) return cfail(GSDF_ERR_INVALID, "null argument");
+    const gsdf_color_state* S = &c->color;
+    *n_tris = 0;
+    if (S->n == 0) return GSDF_OK;
+    if (S->n > (long long)INT_MAX) return cfail(GSDF_ERR_INVALID, "gsdf_color_mesh: more than 2^31 - 1 Hr voxels");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t N = (size_t)S->n;
+    const long long cap = max_tris > 0 ? (long long)max_tris : 0;
+    gsdf_dev<int> d_box;
+    HIP_TRY(d_box.alloc(6));
+    int box[6] = { INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN };
+    HIP_TRY(hipMemcpyAsync(d_box, box, sizeof(box), hipMemcpyHostToDevice, c->stream));
+    /* few workgroups: every wave ends in 6 atomics on the same words (1024 workgroups: 220 us on 2 x 10^5 keys) */
+    hipLaunchKernelGGL(k_hr_bbox, dim3((unsigned int)std::min<size_t>((N + 255) / 256, 64)), dim3(256), 0, c->stream, S->keys.get(), N, d_box.get());
+    HIP_TRY(hipMemcpyAsync(box, d_box, sizeof(box), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int a = 0; a < 3; ++a)                                                 /* fine cells 0 .. 2 extent - 1 must fit the sweep key */
+        if (2ll * ((long long)box[3 + a] - box[a] + 1) > (1ll << GSDF_HR_KEY_BITS))
+            return cfail(GSDF_ERR_INVALID, "gsdf_color_mesh: the snapshot's bounding box spans more than 2^19 voxels on an axis (the sweep key holds 20 bits per fine coordinate)");
+    gsdf_dev<signed char> d_tab;
+    gsdf_dev<float> d_tris;
+    gsdf_dev<uint32_t> d_cols;
+    gsdf_dev<unsigned long long> d_keys;
+    HIP_TRY(d_tab.alloc(256 * 16));
+    if (cap) HIP_TRY(d_tris.alloc((size_t)cap * 9));
+    if (cap) HIP_TRY(d_cols.alloc((size_t)cap * 3));
+    if (cap) HIP_TRY(d_keys.alloc((size_t)cap));
+    HIP_TRY(hipMemcpyAsync(d_tab, GSDF_MC_TRI_TABLE, 256 * 16, hipMemcpyHostToDevice, c->stream));   /* the Hr triTable (:96-352) is the classic one */
+    HIP_TRY(hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream));
+    hr_mesh_args a;
+    a.keys = S->keys; a.rows = S->rows; a.n = S->n;
+    for (int k = 0; k < 3; ++k) { a.mn[k] = box[k]; a.mx[k] = box[3 + k]; }
+    a.vs = S->vs; a.iso = iso; a.tri_table = d_tab;
+    a.tris = d_tris; a.cols = d_cols; a.skeys = d_keys; a.counter = c->counter; a.max_tris = cap;
+    hipLaunchKernelGGL(k_hr_mesh, dim3((unsigned int)((8 * N + 255) / 256)), dim3(256), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    unsigned long long n = 0;
+    HIP_TRY(hipMemcpyAsync(&n, c->counter, sizeof(n), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    /* the reference's order (fine z-y-x sweep, triangles of a cube in table order) = ascending sweep key, as gsdf_extract_mesh */
+    if (n && n <= (unsigned long long)cap) {
+        const size_t got = (size_t)n;
+        gsdf_dev<unsigned long long> d_keys2;
+        gsdf_dev<uint32_t> d_idx, d_idx2;
+        gsdf_dev<float> d_sorted;
+        gsdf_dev<uint8_t> d_bytes;
+        gsdf_dev<void> d_tmp;
+        size_t tmp_bytes = 0;
+        HIP_TRY(d_keys2.alloc(got));
+        HIP_TRY(d_idx.alloc(got));
+        HIP_TRY(d_idx2.alloc(got));
+        HIP_TRY(d_sorted.alloc(got * 9));
+        HIP_TRY(gsdf_sort_pairs_u64(nullptr, &tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, got, c->stream));
+        HIP_TRY(d_tmp.alloc(tmp_bytes ? tmp_bytes : 8));
+        gsdf_launch_iota(c->stream, d_idx, got);
+        HIP_TRY(gsdf_sort_pairs_u64(d_tmp, &tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, got, c->stream));
+        gsdf_launch_gather_tris(c->stream, d_tris, d_idx2, d_sorted, got);
+        HIP_TRY(hipMemcpyAsync(triangles_out, d_sorted, got * 9 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        if (colors_out) {
+            HIP_TRY(d_bytes.alloc(got * 9));
+            hipLaunchKernelGGL(k_hr_gather_cols, dim3((unsigned int)((got * 9 + 255) / 256)), dim3(256), 0, c->stream, d_cols.get(), d_idx2.get(),
+                               d_bytes.get(), got);
+            HIP_TRY(hipMemcpyAsync(colors_out, d_bytes, got * 9, hipMemcpyDeviceToHost, c->stream));
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    *n_tris = (int64_t)n;                                                      /* total found, also when it exceeds max_tris */
+    if (n > (unsigned long long)cap && cap) return cfail(GSDF_ERR_INVALID, "gsdf_color_mesh: max_tris too small (n_tris holds the need)");
     return GSDF_OK;
 }

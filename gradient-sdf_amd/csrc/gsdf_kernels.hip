@@ -2994,19 +2994,6 @@ __global__ __launch_bounds__(256) void k_mesh_bbox(gsdf_table tab, size_t n_slot
     }
 }
 
-__device__ __forceinline__ gsdf_v3 mesh_interpolate(float t0, float t1, gsdf_v3 v0, gsdf_v3 v1, float iso) {
-    if (fabs((double)(iso - t0)) < 1e-7) return v0;                        /* :645-650 (float difference, double compare) */
-    if (fabs((double)(iso - t1)) < 1e-7) return v1;
-    if (fabs((double)(t0 - t1)) < 1e-7) return v0;
-    double mu = (double)((iso - t0) / (t1 - t0));
-    if (mu > 1.0) mu = 1.0; else if (mu < 0) mu = 0.0;
-    gsdf_v3 v;
-    v.x = (float)((double)v0.x + mu * (double)(v1.x - v0.x));
-    v.y = (float)((double)v0.y + mu * (double)(v1.y - v0.y));
-    v.z = (float)((double)v0.z + mu * (double)(v1.z - v0.z));
-    return v;
-}
-
 __global__ __launch_bounds__(256) void k_mesh(gsdf_table tab, size_t n_slots, float vs, float iso, const int* __restrict__ mn,
                                                const signed char* __restrict__ tri_table, float* __restrict__ tris,
                                                unsigned long long* __restrict__ keys, unsigned long long* counter, long long max_tris) {

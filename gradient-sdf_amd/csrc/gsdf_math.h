@@ -73,6 +73,23 @@ GSDF_HD float gsdf_weight(float sdf, float T, float inv_T) {
 /* Sdf::truncate -- sdf_tracker/Sdf.h:72-74 */
 GSDF_HD float gsdf_truncate(float sdf, float T) { return fmaxf(-T, fminf(T, sdf)); }
 
+/* interpolate of the marching cubes -- mesh/LayeredMarchingCubesNoColor.cpp:642-662 and, word for word,
+ * mesh/HrLayeredMarchingCubes.cpp:723-743 (there also for colours): float differences compared in double against 1e-7, mu a
+ * float quotient held in double and clamped, the blend in double rounded once.  Shared by k_mesh (gsdf_kernels.hip) and
+ * k_hr_mesh (gsdf_color.hip): one definition, moved here unchanged. */
+GSDF_HD gsdf_v3 mesh_interpolate(float t0, float t1, gsdf_v3 v0, gsdf_v3 v1, float iso) {
+    if (fabs((double)(iso - t0)) < 1e-7) return v0;                        /* :645-650 (float difference, double compare) */
+    if (fabs((double)(iso - t1)) < 1e-7) return v1;
+    if (fabs((double)(t0 - t1)) < 1e-7) return v0;
+    double mu = (double)((iso - t0) / (t1 - t0));
+    if (mu > 1.0) mu = 1.0; else if (mu < 0) mu = 0.0;
+    gsdf_v3 v;
+    v.x = (float)((double)v0.x + mu * (double)(v1.x - v0.x));
+    v.y = (float)((double)v0.y + mu * (double)(v1.y - v0.y));
+    v.z = (float)((double)v0.z + mu * (double)(v1.z - v0.z));
+    return v;
+}
+
 /* MapGradPixelSdf::float2vox, one component -- MapGradPixelSdf.h:74-77 (std::round = half away from zero) */
 /* std::round as trunc(x + copysign(0.5 - 2^-25, x)): bit-identical to roundf for EVERY float (checked exhaustively,
  * tools/round_check.c) in 3 VALU operations; the generic lowering (trunc, |x - t| >= 0.5, copysign, add) takes 6. */

@@ -7,7 +7,7 @@
  * reference copies the map into its SdfHrMap (init :136-162), so later changes of the map do not reach the result, here as there.
  * computeColor() is kept for the reference's call sequence; the snapshot it would fill is already filled.
  * The map must have been fused with visibility tracking (MapGradPixelSdf::enable_vis()); at most 64 keyframes.
- * extractMesh (HrLayeredMarchingCubes) is not provided.
+ * extractMesh (HrLayeredMarchingCubes) lives in HrLayeredMarchingCubes.h, as a free function over the same snapshot.
  */
 #ifndef GSDF_HOST_COLOR_UPSAMPLER_H_
 #define GSDF_HOST_COLOR_UPSAMPLER_H_

@@ -275,6 +275,29 @@ int gsdf_color_export(gsdf_ctx* c, int32_t* keys, float* rows, int64_t max_n, in
 int gsdf_color_cloud(gsdf_ctx* c, float* rows9, int64_t max_n, int64_t* n);
 /* Hr voxels and observations (voxel x keyframe pairs that counted) of the snapshot (measurement only) */
 int gsdf_color_counters(gsdf_ctx* c, int64_t* voxels, int64_t* observations);
+/* ColorUpsampler::extractMesh -- HrLayeredMarchingCubes::computeIsoSurface (mesh/HrLayeredMarchingCubes.cpp:359-822)
+ * over the snapshot of the last gsdf_color_compute.
+ * Marching cubes over the FINE grid of the snapshot: 2 x 2 x 2 cells per Hr voxel, cell 2 (X - min) + bit per axis holding d[i]
+ * and the colour of sub-voxel i as bytes ((unsigned char)(c * 255); a NaN colour -- no keyframe counted -- is 0).  min / max are
+ * the bounding box of ALL snapshot keys; the sweep visits the cubes anchored at x < dim - 2 per axis (dim = 2 extent, :410-417),
+ * so no cube is anchored inside a voxel of the box's maximal coarse layer.  A cube is skipped when one of its 8 cells lies in
+ * a voxel the snapshot does not hold or has weight 0.  Cube index (tsdf > iso), corner / edge numbering, interpolate and the
+ * triangle table are those of gsdf_extract_mesh (the Hr triTable equals include/gsdf_mc_tables.h entry for entry).  Vertices
+ * are 0.5f * ((float)i * vs) - origin with origin = -(float)min * vs (voxelToWorld :817-821): sub-voxel 0 sits on the voxel
+ * centre and sub-voxel 1 half a voxel further, NOT at -+ 1/4 voxel as in gsdf_color_cloud -- the reference's mesh, kept.  Vertex
+ * colours are getColor's (:756-773): bytes / 255 in float, interpolate with the endpoints in the order of the getColor calls
+ * (for edges 2, 3, 6 and 7 the reverse of the vertex's), * 255 truncated to a byte.
+ * ONE deliberate deviation: the reference reads green at idx + 1 and blue at idx + 2 (:764-766, its own TODO "seems wrong"),
+ * bytes of neighbouring cells of its 4-layer window that are stale or past the buffer -- not a function of the map; here red,
+ * green and blue are read at the cell's own index.
+ * Conventions of gsdf_extract_mesh: max_tris = 0 sizes the buffer; a buffer too small gives GSDF_ERR_INVALID with the need in
+ * *n_tris; no vertex de-duplication; degenerate triangles are dropped (:789); output in the reference's sweep order (fine z,
+ * then y, then x, then the triangle number within the cube).  colors_out is nullable.  Only the snapshot is read; table,
+ * snapshot and cloud stay as they are.  GSDF_ERR_INVALID before a compute, and for a bounding box of more than 2^19 voxels on
+ * an axis (the 64-bit sweep key holds 20 bits per fine coordinate). */
+int gsdf_color_mesh(gsdf_ctx* c, float iso, float* triangles_out /* 9 per triangle */,
+                    uint8_t* colors_out /* 9 per triangle: r,g,b per vertex; nullable */,
+                    int64_t max_tris, int64_t* n_tris);
 
 /* additive merge of raw sums into this table (frame-sharded fusion) */
 int gsdf_merge_raw(gsdf_ctx* c, const int32_t* keys, const float* payload_raw, int64_t n);

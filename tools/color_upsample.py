@@ -7,7 +7,11 @@ key poses, then the colour pass with the pre-BA poses (as the reference does).  
   * Hr voxels, observations (voxel x keyframe pairs that counted) and cloud points,
   * the algorithmic bytes: per observation 8 sub-voxels x 4 taps x 12 B; per Hr voxel its 32 B record, its vis_ words and the
     37-float row it writes,
-  * the numpy restatement (tests/color_upsampler_ref.py) on the same state, 1 core, as the CPU figure.
+  * the numpy restatement (tests/color_upsampler_ref.py) on the same state, 1 core, as the CPU figure,
+  * with --mesh PATH: the coloured sub-voxel mesh of the snapshot (gsdf_color_mesh, ColorUpsampler::extractMesh) written to PATH
+    as the reference's PLY, its triangle count and the median wall time of gsdf_color_mesh (sizing call + exact-size call, as
+    GradSdf.color_mesh makes them); for scale, in the same process, gsdf_extract_mesh on the same map (it visits every voxel
+    record, the Hr sweep only the shell) and, unless --cpu 0, the numpy restatement tests/hr_mesh_ref.py on the same snapshot.
 Per-kernel times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/color_upsample.py` run."""
 import argparse
 import json
@@ -30,6 +34,7 @@ def main():
     ap.add_argument("--ba-it", type=int, default=3)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--cpu", type=int, default=1, help="also time the numpy restatement on the same state (0 = skip)")
+    ap.add_argument("--mesh", metavar="PATH", help="also extract the coloured sub-voxel mesh and write it to PATH (PLY)")
     args = ap.parse_args()
     import __graft_entry__ as graft
     import color_upsampler_ref as CU
@@ -76,6 +81,26 @@ def main():
         t_cpu = time.perf_counter() - t0
         out["cpu_restatement"] = {"kind": "numpy float32 restatement, vectorised over voxels", "cores": 1, "wall_s": round(t_cpu, 3),
                                   "speedup": round(t_cpu / t_c, 1)}
+    if args.mesh:
+        import hr_mesh_ref as HR
+        tris, rgb = g.color_mesh()                                       # warm
+        tm, tx = [], []
+        for _ in range(args.reps):
+            t0 = time.perf_counter(); tris, rgb = g.color_mesh(); tm.append(time.perf_counter() - t0)
+            t0 = time.perf_counter(); plain = g.extract_mesh(); tx.append(time.perf_counter() - t0)
+        with open(args.mesh, "w") as f:
+            f.write(HR.ply_text(tris, rgb))
+        out["mesh"] = {"path": args.mesh, "triangles": int(len(tris)), "color_mesh_ms": round(float(np.median(tm)) * 1e3, 3),
+                       "extract_mesh_ms": round(float(np.median(tx)) * 1e3, 3), "extract_mesh_triangles": int(len(plain)),
+                       "note": "wall times of the sizing call plus the exact-size call (two kernel sweeps, one sort, one copy)"}
+        if args.cpu:
+            keys, rows = g.color_export()
+            t0 = time.perf_counter()
+            rt, rc = HR.compute(keys, rows, vs)
+            t_cpu = time.perf_counter() - t0
+            out["mesh"]["cpu_restatement"] = {"kind": "numpy restatement of the layered sweep, vectorised over one z-layer", "cores": 1,
+                                              "wall_s": round(t_cpu, 3), "speedup": round(t_cpu / float(np.median(tm)), 1),
+                                              "identical": bool(np.array_equal(rt.view(np.uint32), tris.view(np.uint32)) and np.array_equal(rc, rgb))}
     print(json.dumps(out))
     g.close()
 
