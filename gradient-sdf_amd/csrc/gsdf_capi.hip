@@ -70,9 +70,6 @@ void prof_collect(gsdf_ctx* c) {
 int status_to_code(int status) {
     if (status & GSDF_STATUS_TABLE_FULL) return fail(GSDF_ERR_TABLE_FULL, "voxel hash table full (probe budget exhausted)");
     if (status & GSDF_STATUS_KEY_RANGE) return fail(GSDF_ERR_KEY_RANGE, "voxel index outside the packable +-2^20 range");
-    if (status & GSDF_STATUS_TRACK_ABORT)
-        return fail(GSDF_ERR_HIP, "tracking: the workgroups of the one-launch optimize() were not co-resident (GPU shared with another "
-                                  "process?); that optimize() was abandoned -- set GSDF_PERSIST=0 to use one launch per pass");
     return GSDF_OK;
 }
 
@@ -385,26 +382,6 @@ void track_jobs(track_frame& f, float conv, float damping, int sampling) {
     tp.head_done = 0;
 }
 
-/* the whole optimize() as one launch; the frame's fusion, gated on the device by done && converged, right behind it */
-int track_one_launch(track_frame& f) {
-    gsdf_ctx* c = f.c;
-    f.tp.pass_index = 0;
-    f.tp.rot = 0;
-    f.tp.progress = c->progress.dev();
-    {
-        prof_scope ps(c, 2);
-        gsdf_launch_track_all(c->stream, f.g, f.depth, c->tab, c->st, c->frame.track_rows, c->frame.track_abort, c->track_blocks, f.tp,
-                              f.fuse_after ? &f.nj : nullptr);
-    }
-    if (f.fuse_after) {
-        const int rc = f.queue_fusion();
-        if (rc) return rc;
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GSDF_ERR_HIP, std::string("tracking launch: ") + hipGetErrorString(e));
-    return GSDF_OK;
-}
-
 /* optimize() as batches of per-pass launches, the host following the device between them (see enqueue_track) */
 int track_batched(track_frame& f, int base) {
     gsdf_ctx* c = f.c;
@@ -494,8 +471,6 @@ int enqueue_track(gsdf_ctx* c, const float* depth_dev, int iters, float conv, fl
     if (iters > 0x7FFF) return fail(GSDF_ERR_INVALID, "num_iterations must be <= 32767");
     track_jobs(f, conv, damping, sampling);
     const int base = c->map_type == GSDF_MAP_BASE;
-    /* (k_track_all has the grad gather only: a base context runs the per-pass launches) */
-    if (sampling == 1 && !base && c->persist && c->frame.track_rows && c->track_blocks <= 2 * GSDF_TRACK_MAXBLK) return track_one_launch(f);
     const int rc = track_batched(f, base);
     if (rc) return rc;
     hipError_t e = hipGetLastError();
@@ -705,7 +680,6 @@ static int create_impl(gsdf_ctx** out, float voxel_size, float trunc_dist, int c
         }
         if ((env = getenv("GSDF_NEXT_BATCH")) && atoi(env) >= 1) c->next_batch = atoi(env);
         if ((env = getenv("GSDF_LAZY_FUSE"))) c->lazy_fuse = atoi(env);
-        if ((env = getenv("GSDF_PERSIST"))) c->persist = atoi(env);
         if ((env = getenv("GSDF_FAR_TABLE"))) c->far_table = atoi(env);       /* experiments: 0 / 1 pin the fusion kernel's table size */
         /* auto-grow: entries the host may be ahead of the newest count.  Counts are queued every fourth entry while the load
          * is low, so a lag below 8 could never be "safe" between two of them: smaller values are raised to 8 */
@@ -835,10 +809,6 @@ int gsdf_normals_init(gsdf_ctx* c, int W, int H, const float K[9], int win) {
     const int track_blocks = N >= (size_t)1 << 20 ? 2 * GSDF_TRACK_MAXBLK : N >= (size_t)1 << 18 ? GSDF_TRACK_MAXBLK
                                                   : (int)std::max<size_t>(1, (N + 511) / 512);
     HIP_TRY(alloc_zeroed(f.partials, (size_t)3 * GSDF_TRACK_ROWSET, c->stream));
-    if (track_blocks <= 2 * GSDF_TRACK_MAXBLK) {
-        HIP_TRY(alloc_zeroed(f.track_rows, gsdf_track_all_rows_bytes(track_blocks), c->stream));
-        HIP_TRY(alloc_zeroed(f.track_abort, 1, c->stream));
-    }
     const int fuse_blocks = gsdf_fuse_grid_blocks(W, H);
     /* per set of normal planes: the statistics of the frame's fusion tiles (depth range, valid pixels), written with the normals */
     HIP_TRY(alloc_zeroed(f.tile_stats, (size_t)3 * fuse_blocks * 4, c->stream));

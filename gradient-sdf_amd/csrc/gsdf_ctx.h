@@ -143,8 +143,6 @@ struct gsdf_frame_bufs {
     gsdf_dev<float> normals;                       /* 3 sets of 3 planes */
     gsdf_dev<uint32_t> tile_stats;                 /* per set: [fuse_blocks][4] statistics of the frame's fusion tiles (gsdf_kernels.hip: gsdf_tile_stats) */
     gsdf_dev<double> partials;                     /* 3 rotating buffers of tracker partial sums */
-    gsdf_dev<void> track_rows;                     /* k_track_all: the workgroups' rows of sums, two buffers (pass parity) */
-    gsdf_dev<unsigned int> track_abort;            /* k_track_all: abort word */
     gsdf_dev<unsigned long long> blk_counters;
     gsdf_dev<unsigned int> tile_flags;             /* per-tile hand-off flags of k_fuse */
     gsdf_dev<uint32_t> tile_order;                 /* launch order of the fusion tiles (gsdf_fuse_tile_order) */
@@ -212,7 +210,6 @@ struct gsdf_ctx {
     gsdf_dev<gsdf_dev_state> st;
     unsigned int track_rot = 0;                    /* tracker launches issued so far, mod 3 (selects the sum buffers) */
     int track_blocks = 0;
-    int persist = 0;                               /* optimize() as one launch (k_track_all) instead of one launch per pass */
     int fuse_blocks = 0;                           /* tiles of a frame */
     unsigned int deferred_cap = 0;
     unsigned int fuse_tag = 0;                     /* serial of the last fusion launch */

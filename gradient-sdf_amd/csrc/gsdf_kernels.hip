@@ -660,9 +660,206 @@ __device__ __forceinline__ void fuse_log_row(const fuse_args& a) {
     st->log_rows = r + 1;
 }
 
-/* (the tracker's head, defined with k_track_pass below) */
+/* ------------------------------------------------------------------------------------------------
+ * The tracker's head (the pass kernel itself is k_track_pass, further down): reduce the group sums of the previous pass, solve,
+ * stop test, pose update, publish.  Written once, here, in front of its two users: k_track_pass performs it at the top of every
+ * launch, fuse_head (k_fuse<.., HEAD>) performs the closing one inside the frame's first gated fusion launch.
+ * ---------------------------------------------------------------------------------------------- */
+/* One Gauss-Newton step from the 29 sums (RigidPointOptimizer.cpp:86-98): solve, test, apply.  `passes` counts
+ * this pass.  Identical arithmetic wherever it runs (every workgroup computes it redundantly).
+ *
+ * The head's solve is executed by ONE wave whose 64 lanes all do the same scalar work, at the top of every launch with a
+ * cold instruction cache: through round 4 it reproduced gsdf_llt_solve6 / gsdf_se3_exp_mul bit for bit (6 correctly
+ * rounded square roots, 27 divisions, four full-range sinf / cosf: ~1 200 dependent instructions, 2.3-2.9 us of a 9.5 us
+ * pass) -- exactness that bought no parity, because its INPUTS already differ from the oracle's in their last bits
+ * (pairwise float / f64 group sums here, one sequential float sum there).  The common case is now the same algorithm in
+ * <= 1-ulp forms (trk_llt_solve6_fast, trk_se3_exp_mul_fast below): hardware reciprocal / reciprocal square root with one
+ * Newton step through FMA, FMA dot products, and sin / cos as short polynomials for rotation steps below 0.1 rad.  The
+ * exact forms stay for what the fast ones do not cover: a non-positive pivot (Eigen stops the factorisation there and
+ * solves on what it has), theta^2 below Sophus' epsilon (its series branch) and rotation steps of 0.1 rad or more. */
+__device__ __forceinline__ float trk_lane_value(float v, int lane_const) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane_const));
+}
+/* 1 / x and 1 / sqrt(x): v_rcp_f32 / v_rsq_f32 (1 ulp) + one Newton step in FMA arithmetic => below 1 ulp */
+__device__ __forceinline__ float trk_rcp(float x) {
+    const float r = __builtin_amdgcn_rcpf(x);
+    return __builtin_fmaf(__builtin_fmaf(-x, r, 1.f), r, r);
+}
+__device__ __forceinline__ float trk_rsq(float x) {
+    const float r = __builtin_amdgcn_rsqf(x);
+    const float e = __builtin_fmaf(-(x * r), 0.5f * r, 0.5f);      /* (1 - x r^2) / 2 */
+    return __builtin_fmaf(r, e, r);
+}
+/* H.llt().solve(g) (RigidPointOptimizer.cpp:86) in the structure of Eigen's unblocked llt_inplace and unrolled triangular
+ * solves -- pivot = A(k,k) - (sum of squares), column = (A21 - A20 * A10^T) / pivot root, rhs(i) = (rhs(i) - dot) / diagonal
+ * -- with the reciprocal root of the pivot kept in the diagonal, so that every division is a multiplication.
+ * Returns false (x untouched) when a pivot is not positive: the caller takes the exact path then. */
+__device__ __forceinline__ bool trk_llt_solve6_fast(const float* Hm, const float* g, float* x) {
+    float L[36];                                               /* lower triangle; L(k,k) holds 1 / sqrt(pivot) */
+    bool positive = true;                                      /* every pivot so far was > 0 (or NaN) */
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        float sq = 0.f;
+#pragma unroll
+        for (int j = 0; j < k; ++j) sq = __builtin_fmaf(L[6 * k + j], L[6 * k + j], sq);
+        const float d = Hm[6 * k + k] - sq;
+        positive = positive && !(d <= 0.f);
+        const float ri = trk_rsq(d);
+        L[6 * k + k] = ri;
+#pragma unroll
+        for (int i = k + 1; i < 6; ++i) {
+            float c = 0.f;
+#pragma unroll
+            for (int j = 0; j < k; ++j) c = __builtin_fmaf(L[6 * i + j], L[6 * k + j], c);
+            L[6 * i + k] = (Hm[6 * i + k] - c) * ri;
+        }
+    }
+    if (!positive) return false;
+    float y[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        float c = 0.f;
+#pragma unroll
+        for (int j = 0; j < i; ++j) c = __builtin_fmaf(L[6 * i + j], y[j], c);
+        y[i] = (g[i] - c) * L[6 * i + i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        float c = 0.f;
+#pragma unroll
+        for (int j = i + 1; j < 6; ++j) c = __builtin_fmaf(L[6 * j + i], x[j], c);
+        x[i] = (y[i] - c) * L[6 * i + i];
+    }
+    return true;
+}
+/* The exact forms, spread over lanes WITHOUT changing a single operation or its order (bit-identical to gsdf_llt_solve6 /
+ * gsdf_se3_exp_mul in every lane).  Rare paths since round 5. */
+__device__ __forceinline__ void trk_se3_exp_mul_wave(const float* xi, float* pose7) {
+    float trig[4] = { 0.f, 1.f, 0.f, 1.f };
+    const float theta_sq = gsdf_se3_theta_sq(xi);
+    if (!(theta_sq < GSDF_SOPHUS_EPS * GSDF_SOPHUS_EPS)) {
+        const float theta = sqrtf(theta_sq), half = 0.5f * theta;
+        const float arg = (threadIdx.x & 1u) ? theta : half;   /* sinf / cosf of theta / 2 and of theta evaluated once: odd lanes take theta */
+        const float sn = sinf(arg), cs = cosf(arg);
+        trig[0] = trk_lane_value(sn, 0); trig[1] = trk_lane_value(cs, 0);
+        trig[2] = trk_lane_value(sn, 1); trig[3] = trk_lane_value(cs, 1);
+    }
+    gsdf_se3_exp_mul_trig(xi, pose7, trig);
+}
+/* sin / cos for |x| < 0.1: Taylor polynomials whose first omitted terms are below 3e-14 / 3e-13 relative, in FMA Horner form */
+__device__ __forceinline__ float trk_sin_small(float x, float x2) {
+    float p = __builtin_fmaf(x2, -1.f / 5040.f, 1.f / 120.f);
+    p = __builtin_fmaf(x2, p, -1.f / 6.f);
+    return __builtin_fmaf(x, x2 * p, x);
+}
+__device__ __forceinline__ float trk_cos_small(float x2) {
+    float p = __builtin_fmaf(x2, -1.f / 720.f, 1.f / 24.f);
+    p = __builtin_fmaf(x2, p, -0.5f);
+    return __builtin_fmaf(x2, p, 1.f);
+}
+/* pose7 = SE3::exp(xi) * pose7 with Sophus' formulas as written (gsdf_se3_exp_mul_trig) in <= 1-ulp forms, for
+ * eps^2 <= theta^2 < 0.01; everything else goes through the exact path. */
+__device__ __forceinline__ void trk_se3_exp_mul_fast(const float* xi, float* pose7) {
+    const float theta_sq = gsdf_se3_theta_sq(xi);
+    if (__builtin_expect(!(theta_sq >= GSDF_SOPHUS_EPS * GSDF_SOPHUS_EPS && theta_sq < 0.01f), 0)) {
+        trk_se3_exp_mul_wave(xi, pose7);
+        return;
+    }
+    const float rth = trk_rsq(theta_sq);                       /* 1 / theta */
+    const float theta = theta_sq * rth, half = 0.5f * theta;
+    const float tsq = theta * theta, hsq = half * half;
+    const float rth2 = rth * rth;
+    const float imag = trk_sin_small(half, hsq) * rth;         /* sin(theta / 2) / theta */
+    const float real = trk_cos_small(hsq);
+    const float a = (1.f - trk_cos_small(tsq)) * rth2;         /* (1 - cos theta) / theta^2 */
+    const float b = (theta - trk_sin_small(theta, tsq)) * (rth2 * rth);   /* (theta - sin theta) / theta^3 */
+    float qn[4];
+    gsdf_se3_exp_mul_parts(xi, pose7, imag, real, false, a, b, qn);
+    const float rl = trk_rsq(qn[0] * qn[0] + qn[1] * qn[1] + qn[2] * qn[2] + qn[3] * qn[3]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) pose7[3 + i] = qn[i] * rl;
+}
+
+/* called by a full wave (all 64 lanes active, same arguments in every lane) */
 __device__ __forceinline__ void trk_solve_update(const float* tot, float damping, float conv_sq, int passes, int max_passes,
-                                                 int no_solve, bool exact_solve, float pose[7], int* done, int* converged);
+                                                 int no_solve, bool exact_solve /* test build: the round-4 arithmetic */,
+                                                 float pose[7], int* done, int* converged) {
+    float gvec[6], Hm[36];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) gvec[i] = tot[1 + i];
+    int q = 7;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j) { Hm[6 * i + j] = tot[q]; Hm[6 * j + i] = tot[q]; ++q; }
+    float xi[6];
+    if (no_solve) { for (int i = 0; i < 6; ++i) xi[i] = 1.f; }            /* experiment switch */
+    else if (exact_solve || __builtin_expect(!trk_llt_solve6_fast(Hm, gvec, xi), 0))
+        gsdf_llt_solve6(Hm, gvec, xi);                                    /* RigidPointOptimizer.cpp:86 */
+#pragma unroll
+    for (int i = 0; i < 6; ++i) xi[i] = damping * xi[i];
+    const float nrm = gsdf_sum3(xi[0] * xi[0], xi[1] * xi[1], xi[2] * xi[2]) +
+                      gsdf_sum3(xi[3] * xi[3], xi[4] * xi[4], xi[5] * xi[5]);
+    *done = 0; *converged = 0;
+    if (nrm < conv_sq) {                                                  /* :88-91 (xi is NOT applied) */
+        *converged = 1;
+        *done = 1;
+    } else {
+        bool nan = false;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) nan = nan || isnan(xi[i]);
+        if (!nan && !no_solve) {                                          /* :94-95 */
+            float mxi[6];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) mxi[i] = -xi[i];
+            if (exact_solve) trk_se3_exp_mul_wave(mxi, pose);
+            else trk_se3_exp_mul_fast(mxi, pose);
+        }
+        if (passes >= max_passes) *done = 1;                              /* :98 return false */
+    }
+}
+
+/* The 29 sums of the pass whose group sums are in acc_prev, in every lane: lane v < 29 adds the GSDF_TRACK_GROUPS group sums of
+ * value v in increasing order (all loads in flight at once), `v_readlane` hands the totals to every lane.
+ * Called by a full wave. */
+__device__ __forceinline__ void trk_head_totals(const double* acc_prev, int lane, float (&tot)[GSDF_TRACK_NSUM]) {
+    double gs = 0.0;
+    if (lane < GSDF_TRACK_NSUM) {
+        double part[GSDF_TRACK_GROUPS];
+#pragma unroll
+        for (int grp = 0; grp < GSDF_TRACK_GROUPS; ++grp) part[grp] = acc_prev[grp * 32 + lane];
+        gs = part[0];
+#pragma unroll
+        for (int grp = 1; grp < GSDF_TRACK_GROUPS; ++grp) gs += part[grp];
+    }
+    const float totv = (float)gs;
+#pragma unroll
+    for (int i = 0; i < GSDF_TRACK_NSUM; ++i) tot[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(totv), i));
+}
+
+/* The state behind the head of launch k, for the next launch, the gated fusion launches and the host.  Called by ONE lane (the
+ * first of the launch's workgroup 0). */
+__device__ __forceinline__ void trk_head_publish(gsdf_dev_state* st, int k, const float pose[7], int done, int converged, int passes,
+                                                 float hits, unsigned int* progress, unsigned int serial) {
+    gsdf_trk_buf& o = st->trk[k & 1];
+#pragma unroll
+    for (int i = 0; i < 7; ++i) { o.pose7[i] = pose[i]; st->pose7[i] = pose[i]; }
+    o.done = done; o.converged = converged; o.passes = passes;
+    /* make `done` sticky in the other parity as well: launches that the host queued beyond the end of this optimize() must not
+     * take the older buffer for live state and redo the step (workgroups of THIS launch that still read it return early, which
+     * is what they do anyway; the waves of a k_fuse<.., HEAD> launch whose wait expired read it at agent scope: see fuse_head) */
+    if (done) __hip_atomic_store(&st->trk[(k - 1) & 1].done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    gsdf_quat_to_R(pose + 3, st->R);
+    st->converged = converged;
+    st->done = done;
+    st->passes = passes;
+    st->last_hits = hits;
+    st->n_hit += (unsigned long long)hits;
+    /* progress for the host's adaptive pass issue (pinned host memory, system scope) */
+    if (progress)                    /* one word, so the host reads a consistent (passes, done) pair */
+        __hip_atomic_store(&progress[0], (serial << 16) | (done ? 0x8000u : 0u) | (unsigned int)(passes & 0x7FFF),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 
 /* k_fuse<.., HEAD>: the head of tracker launch a.hd.k (see k_fuse).  On return (pose, done, conv) are the state behind that head:
  * computed by the `solver` wave (workgroup 0's first) -- or, when optimize() had ended in an earlier launch, read by it from a.st,
@@ -721,46 +918,17 @@ __device__ __forceinline__ void fuse_head(const fuse_args& a, int tid, bool solv
 #pragma unroll
         for (int i = 0; i < 7; ++i) pose[i] = st->pose7[i];
     } else {
-        /* the head itself, as in k_track_pass: lane v < 29 adds the group sums of value v in increasing order, readlane hands the
-         * totals to every lane, the solve runs in every lane alike.  (A wave whose wait expired: rows, in.pose7 and in.passes are
-         * not written in this launch.) */
-        const double* acc_prev = a.hd.rows + (size_t)a.hd.rot_prev * GSDF_TRACK_ROWSET;
-        double gs = 0.0;
-        if (hlane < GSDF_TRACK_NSUM) {
-            double part[GSDF_TRACK_GROUPS];
-#pragma unroll
-            for (int grp = 0; grp < GSDF_TRACK_GROUPS; ++grp) part[grp] = acc_prev[grp * 32 + hlane];
-            gs = part[0];
-#pragma unroll
-            for (int grp = 1; grp < GSDF_TRACK_GROUPS; ++grp) gs += part[grp];
-        }
+        /* the head itself, the one k_track_pass performs: the totals in every lane, the solve in every lane alike.  (A wave whose
+         * wait expired: rows, in.pose7 and in.passes are not written in this launch.) */
 #pragma unroll
         for (int i = 0; i < 7; ++i) pose[i] = in.pose7[i];
         hpasses = in.passes + 1;
-        const float totv = (float)gs;
         float tot[GSDF_TRACK_NSUM];
-#pragma unroll
-        for (int i = 0; i < GSDF_TRACK_NSUM; ++i) tot[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(totv), i));
+        trk_head_totals(a.hd.rows + (size_t)a.hd.rot_prev * GSDF_TRACK_ROWSET, hlane, tot);
         trk_solve_update(tot, a.hd.damping, a.hd.conv_sq, hpasses, a.hd.max_passes, GSDF_EXPERIMENT(a.hd.debug, 1),
                          GSDF_EXPERIMENT(a.hd.debug, 4), pose, &hdone, &hconv);
-        if (solver && hlane == 0) {
-            /* published as k_track_pass's workgroup 0 publishes its head (see there) ... */
-            gsdf_dev_state* st = a.st;
-            gsdf_trk_buf& o = st->trk[a.hd.k & 1];
-#pragma unroll
-            for (int i = 0; i < 7; ++i) { o.pose7[i] = pose[i]; st->pose7[i] = pose[i]; }
-            o.done = hdone; o.converged = hconv; o.passes = hpasses;
-            if (hdone) __hip_atomic_store(&st->trk[(a.hd.k - 1) & 1].done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            gsdf_quat_to_R(pose + 3, st->R);
-            st->converged = hconv;
-            st->done = hdone;
-            st->passes = hpasses;
-            st->last_hits = tot[28];
-            st->n_hit += (unsigned long long)tot[28];
-            if (a.hd.progress)
-                __hip_atomic_store(&a.hd.progress[0], (a.hd.serial << 16) | (hdone ? 0x8000u : 0u) | (unsigned int)(hpasses & 0x7FFF),
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+        /* published for the later launches and the host ... */
+        if (solver && hlane == 0) trk_head_publish(a.st, a.hd.k, pose, hdone, hconv, hpasses, tot[28], a.hd.progress, a.hd.serial);
     }
     if (solver && hlane == 0) {
         /* ... and for every other wave of THIS launch: the tagged chunks (also when optimize() had ended before the launch) */
@@ -1659,169 +1827,15 @@ void gsdf_launch_track_none(hipStream_t s, gsdf_dev_state* st) { hipLaunchKernel
 #define TRK_CHUNK ((GSDF_TRACK_BLOCK / 128) * 64 * (2 * TRK_PPT - 1))
 #endif
 
-/* One Gauss-Newton step from the 29 sums (RigidPointOptimizer.cpp:86-98): solve, test, apply.  `passes` counts
- * this pass.  Identical arithmetic wherever it runs (every workgroup computes it redundantly).
- *
- * The head's solve is executed by ONE wave whose 64 lanes all do the same scalar work, at the top of every launch with a
- * cold instruction cache: through round 4 it reproduced gsdf_llt_solve6 / gsdf_se3_exp_mul bit for bit (6 correctly
- * rounded square roots, 27 divisions, four full-range sinf / cosf: ~1 200 dependent instructions, 2.3-2.9 us of a 9.5 us
- * pass) -- exactness that bought no parity, because its INPUTS already differ from the oracle's in their last bits
- * (pairwise float / f64 group sums here, one sequential float sum there).  The common case is now the same algorithm in
- * <= 1-ulp forms (trk_llt_solve6_fast, trk_se3_exp_mul_fast below): hardware reciprocal / reciprocal square root with one
- * Newton step through FMA, FMA dot products, and sin / cos as short polynomials for rotation steps below 0.1 rad.  The
- * exact forms stay for what the fast ones do not cover: a non-positive pivot (Eigen stops the factorisation there and
- * solves on what it has), theta^2 below Sophus' epsilon (its series branch) and rotation steps of 0.1 rad or more. */
-__device__ __forceinline__ float trk_lane_value(float v, int lane_const) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane_const));
-}
-/* 1 / x and 1 / sqrt(x): v_rcp_f32 / v_rsq_f32 (1 ulp) + one Newton step in FMA arithmetic => below 1 ulp */
-__device__ __forceinline__ float trk_rcp(float x) {
-    const float r = __builtin_amdgcn_rcpf(x);
-    return __builtin_fmaf(__builtin_fmaf(-x, r, 1.f), r, r);
-}
-__device__ __forceinline__ float trk_rsq(float x) {
-    const float r = __builtin_amdgcn_rsqf(x);
-    const float e = __builtin_fmaf(-(x * r), 0.5f * r, 0.5f);      /* (1 - x r^2) / 2 */
-    return __builtin_fmaf(r, e, r);
-}
-/* H.llt().solve(g) (RigidPointOptimizer.cpp:86) in the structure of Eigen's unblocked llt_inplace and unrolled triangular
- * solves -- pivot = A(k,k) - (sum of squares), column = (A21 - A20 * A10^T) / pivot root, rhs(i) = (rhs(i) - dot) / diagonal
- * -- with the reciprocal root of the pivot kept in the diagonal, so that every division is a multiplication.
- * Returns false (x untouched) when a pivot is not positive: the caller takes the exact path then. */
-__device__ __forceinline__ bool trk_llt_solve6_fast(const float* Hm, const float* g, float* x) {
-    float L[36];                                               /* lower triangle; L(k,k) holds 1 / sqrt(pivot) */
-    bool positive = true;                                      /* every pivot so far was > 0 (or NaN) */
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        float sq = 0.f;
-#pragma unroll
-        for (int j = 0; j < k; ++j) sq = __builtin_fmaf(L[6 * k + j], L[6 * k + j], sq);
-        const float d = Hm[6 * k + k] - sq;
-        positive = positive && !(d <= 0.f);
-        const float ri = trk_rsq(d);
-        L[6 * k + k] = ri;
-#pragma unroll
-        for (int i = k + 1; i < 6; ++i) {
-            float c = 0.f;
-#pragma unroll
-            for (int j = 0; j < k; ++j) c = __builtin_fmaf(L[6 * i + j], L[6 * k + j], c);
-            L[6 * i + k] = (Hm[6 * i + k] - c) * ri;
-        }
-    }
-    if (!positive) return false;
-    float y[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        float c = 0.f;
-#pragma unroll
-        for (int j = 0; j < i; ++j) c = __builtin_fmaf(L[6 * i + j], y[j], c);
-        y[i] = (g[i] - c) * L[6 * i + i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        float c = 0.f;
-#pragma unroll
-        for (int j = i + 1; j < 6; ++j) c = __builtin_fmaf(L[6 * j + i], x[j], c);
-        x[i] = (y[i] - c) * L[6 * i + i];
-    }
-    return true;
-}
-/* The exact forms, spread over lanes WITHOUT changing a single operation or its order (bit-identical to gsdf_llt_solve6 /
- * gsdf_se3_exp_mul in every lane).  Rare paths since round 5. */
-__device__ __forceinline__ void trk_se3_exp_mul_wave(const float* xi, float* pose7) {
-    float trig[4] = { 0.f, 1.f, 0.f, 1.f };
-    const float theta_sq = gsdf_se3_theta_sq(xi);
-    if (!(theta_sq < GSDF_SOPHUS_EPS * GSDF_SOPHUS_EPS)) {
-        const float theta = sqrtf(theta_sq), half = 0.5f * theta;
-        const float arg = (threadIdx.x & 1u) ? theta : half;   /* sinf / cosf of theta / 2 and of theta evaluated once: odd lanes take theta */
-        const float sn = sinf(arg), cs = cosf(arg);
-        trig[0] = trk_lane_value(sn, 0); trig[1] = trk_lane_value(cs, 0);
-        trig[2] = trk_lane_value(sn, 1); trig[3] = trk_lane_value(cs, 1);
-    }
-    gsdf_se3_exp_mul_trig(xi, pose7, trig);
-}
-/* sin / cos for |x| < 0.1: Taylor polynomials whose first omitted terms are below 3e-14 / 3e-13 relative, in FMA Horner form */
-__device__ __forceinline__ float trk_sin_small(float x, float x2) {
-    float p = __builtin_fmaf(x2, -1.f / 5040.f, 1.f / 120.f);
-    p = __builtin_fmaf(x2, p, -1.f / 6.f);
-    return __builtin_fmaf(x, x2 * p, x);
-}
-__device__ __forceinline__ float trk_cos_small(float x2) {
-    float p = __builtin_fmaf(x2, -1.f / 720.f, 1.f / 24.f);
-    p = __builtin_fmaf(x2, p, -0.5f);
-    return __builtin_fmaf(x2, p, 1.f);
-}
-/* pose7 = SE3::exp(xi) * pose7 with Sophus' formulas as written (gsdf_se3_exp_mul_trig) in <= 1-ulp forms, for
- * eps^2 <= theta^2 < 0.01; everything else goes through the exact path. */
-__device__ __forceinline__ void trk_se3_exp_mul_fast(const float* xi, float* pose7) {
-    const float theta_sq = gsdf_se3_theta_sq(xi);
-    if (__builtin_expect(!(theta_sq >= GSDF_SOPHUS_EPS * GSDF_SOPHUS_EPS && theta_sq < 0.01f), 0)) {
-        trk_se3_exp_mul_wave(xi, pose7);
-        return;
-    }
-    const float rth = trk_rsq(theta_sq);                       /* 1 / theta */
-    const float theta = theta_sq * rth, half = 0.5f * theta;
-    const float tsq = theta * theta, hsq = half * half;
-    const float rth2 = rth * rth;
-    const float imag = trk_sin_small(half, hsq) * rth;         /* sin(theta / 2) / theta */
-    const float real = trk_cos_small(hsq);
-    const float a = (1.f - trk_cos_small(tsq)) * rth2;         /* (1 - cos theta) / theta^2 */
-    const float b = (theta - trk_sin_small(theta, tsq)) * (rth2 * rth);   /* (theta - sin theta) / theta^3 */
-    float qn[4];
-    gsdf_se3_exp_mul_parts(xi, pose7, imag, real, false, a, b, qn);
-    const float rl = trk_rsq(qn[0] * qn[0] + qn[1] * qn[1] + qn[2] * qn[2] + qn[3] * qn[3]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) pose7[3 + i] = qn[i] * rl;
-}
-
-/* called by a full wave (all 64 lanes active, same arguments in every lane) */
-__device__ __forceinline__ void trk_solve_update(const float* tot, float damping, float conv_sq, int passes, int max_passes,
-                                                 int no_solve, bool exact_solve /* test build: the round-4 arithmetic */,
-                                                 float pose[7], int* done, int* converged) {
-    float gvec[6], Hm[36];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) gvec[i] = tot[1 + i];
-    int q = 7;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int j = i; j < 6; ++j) { Hm[6 * i + j] = tot[q]; Hm[6 * j + i] = tot[q]; ++q; }
-    float xi[6];
-    if (no_solve) { for (int i = 0; i < 6; ++i) xi[i] = 1.f; }            /* experiment switch */
-    else if (exact_solve || __builtin_expect(!trk_llt_solve6_fast(Hm, gvec, xi), 0))
-        gsdf_llt_solve6(Hm, gvec, xi);                                    /* RigidPointOptimizer.cpp:86 */
-#pragma unroll
-    for (int i = 0; i < 6; ++i) xi[i] = damping * xi[i];
-    const float nrm = gsdf_sum3(xi[0] * xi[0], xi[1] * xi[1], xi[2] * xi[2]) +
-                      gsdf_sum3(xi[3] * xi[3], xi[4] * xi[4], xi[5] * xi[5]);
-    *done = 0; *converged = 0;
-    if (nrm < conv_sq) {                                                  /* :88-91 (xi is NOT applied) */
-        *converged = 1;
-        *done = 1;
-    } else {
-        bool nan = false;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) nan = nan || isnan(xi[i]);
-        if (!nan && !no_solve) {                                          /* :94-95 */
-            float mxi[6];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) mxi[i] = -xi[i];
-            if (exact_solve) trk_se3_exp_mul_wave(mxi, pose);
-            else trk_se3_exp_mul_fast(mxi, pose);
-        }
-        if (passes >= max_passes) *done = 1;                              /* :98 return false */
-    }
-}
-
 /* Gather + normal-equation sums of one pass for this lane's pixels: back-project, voxel lookup (block key from the
- * L2-resident key array, then the 32-byte record), residual, Jacobian.  The lane's pixels of one batch are pix0 + j * pix_stride
+ * L2-resident key array, then the 32-byte record), residual, Jacobian.  The lane's pixels of one batch are pix0 + j * 64
  * (j < PPT: independent gathers in flight), the next batch follows batch_stride pixels further.
- * z_first (nullable): depth of the first batch, already in registers. */
+ * z_first: depth of the first batch, already in registers. */
 template <int PPT>
 __device__ __forceinline__ void trk_gather(const gsdf_frame_geom& g, const gsdf_table& tab, const float* __restrict__ depth,
-                                           const float* z_first, const float pose[7], int pix0, int pix_stride, int batch_stride,
-                                           float (&acc)[GSDF_TRACK_NSUM], unsigned long long* wave_stamp = nullptr,
-                                           const int xy_scale = 1) {
+                                           const float* z_first, const float pose[7], int pix0, int batch_stride,
+                                           float (&acc)[GSDF_TRACK_NSUM], unsigned long long* wave_stamp, const int xy_scale) {
+    constexpr int pix_stride = 64;                                        /* a wave's rows of 64 pixels: see k_track_pass */
     /* wave_stamp (test build, tools/track_waves.py): one word per wave = gather ticks | ticks until the block lookups are done |
      * pixels that passed the z gate | pixels with a voxel, 16 bits each (first batch of pixels) */
     const unsigned long long ws_t0 = wave_stamp ? wall_clock64() : 0ull;
@@ -1840,7 +1854,7 @@ __device__ __forceinline__ void trk_gather(const gsdf_frame_geom& g, const gsdf_
         for (int j = 0; j < PPT; ++j) {
             const int pix = base + j * pix_stride;
             ok[j] = pix < N;
-            z[j] = (z_first && base == pix0) ? z_first[j] : (ok[j] ? depth[pix] : 0.f);
+            z[j] = base == pix0 ? z_first[j] : (ok[j] ? depth[pix] : 0.f);
         }
         /* stage B: back-project, voxel key, block key at the home entry (L2-resident key array) */
         gsdf_v3 p[PPT];
@@ -2028,8 +2042,9 @@ __device__ __forceinline__ base_sample gsdf_base_sample(const gsdf_table& tab, f
  * a pixel's 8-block lookup and 8 record loads are its independent loads in flight. */
 template <int PPT>
 __device__ __forceinline__ void trk_gather_base(const gsdf_frame_geom& g, const gsdf_table& tab, const float* __restrict__ depth,
-                                                const float pose[7], int pix0, int pix_stride, int batch_stride,
-                                                float (&acc)[GSDF_TRACK_NSUM], const int xy_scale = 1) {
+                                                const float pose[7], int pix0, int batch_stride,
+                                                float (&acc)[GSDF_TRACK_NSUM], const int xy_scale) {
+    constexpr int pix_stride = 64;
     float R[9];
     gsdf_quat_to_R(pose + 3, R);                                          /* RigidPointOptimizer.cpp:53-54 */
     const float t[3] = { pose[0], pose[1], pose[2] };
@@ -2169,70 +2184,19 @@ __global__ __launch_bounds__(GSDF_TRACK_BLOCK, BASE ? 2 : 4) void k_track_pass(g
          * them, and is rare), `v_readlane` hands the 29 totals to every lane, the solve runs without an LDS stage; the
          * other waves meet it at ONE barrier (two LDS stages behind three barriers before). */
         const gsdf_trk_buf& in = st->trk[(k - 1) & 1];
-        if (GSDF_EXPERIMENT(tp.debug, 8) && wave != 0) {
-            /* experiment (test build, tracker debug bit 8; tools/track_waves.py warm): while wave 0 solves, the other waves run the
-             * gather of their pixels with the OLD pose and throw the sums away -- a pass moves the pose by a fraction of a voxel, so
-             * the key-array entries and most record lines of the real gather are then in this XCD's L2 (every launch starts with the
-             * L2 invalidated: FETCH ~ algorithmic bytes).  Does the real gather get shorter? */
-            float pose_old[7];
-#pragma unroll
-            for (int i = 0; i < 7; ++i) pose_old[i] = in.pose7[i];
-            float dummy[GSDF_TRACK_NSUM];
-#pragma unroll
-            for (int i = 0; i < GSDF_TRACK_NSUM; ++i) dummy[i] = 0.f;
-            const int xy_scale_w = SAMPLED ? tp.sampling : 1;
-            if constexpr (BASE) {
-                if (trk_heavy) trk_gather_base<TRK_PPT>(g, tab, depth, pose_old, trk_pix0, 64, trk_batch, dummy, xy_scale_w);
-                else trk_gather_base<TRK_PPT - 1>(g, tab, depth, pose_old, trk_pix0, 64, trk_batch, dummy, xy_scale_w);
-            } else {
-                if (trk_heavy) trk_gather<TRK_PPT>(g, tab, depth, z_pre, pose_old, trk_pix0, 64, trk_batch, dummy, nullptr, xy_scale_w);
-                else trk_gather<TRK_PPT - 1>(g, tab, depth, z_pre, pose_old, trk_pix0, 64, trk_batch, dummy, nullptr, xy_scale_w);
-            }
-            if (dummy[28] == -1.f) st->dbg[20] = 1ull;                    /* (never: a count; keeps the loads alive) */
-        }
         if (wave == 0) {
-            double gs = 0.0;
-            if (lane < GSDF_TRACK_NSUM) {
-                double part[GSDF_TRACK_GROUPS];
-#pragma unroll
-                for (int grp = 0; grp < GSDF_TRACK_GROUPS; ++grp) part[grp] = acc_prev[grp * 32 + lane];
-                gs = part[0];
-#pragma unroll
-                for (int grp = 1; grp < GSDF_TRACK_GROUPS; ++grp) gs += part[grp];
-            }
             const int in_done = in.done;
 #pragma unroll
             for (int i = 0; i < 7; ++i) pose[i] = in.pose7[i];
             const int passes = in.passes + 1;
-            if (trk_tr && threadIdx.x == 0) { trk_tr[4] = wall_clock64() + (unsigned long long)(gs != gs) + (unsigned long long)(passes < 0); }   /* sums + state arrived */
+            float tot[GSDF_TRACK_NSUM];                                   /* the 29 sums, in every lane */
+            trk_head_totals(acc_prev, lane, tot);
+            if (trk_tr && threadIdx.x == 0) { trk_tr[4] = wall_clock64() + (unsigned long long)(tot[0] != tot[0]) + (unsigned long long)(passes < 0); }   /* sums + state arrived */
             int done = 1, converged = 0;
             if (!in_done) {                                               /* else: this optimize() already ended */
-                const float totv = (float)gs;
-                float tot[GSDF_TRACK_NSUM];                               /* the 29 sums, in every lane */
-#pragma unroll
-                for (int i = 0; i < GSDF_TRACK_NSUM; ++i) tot[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(totv), i));
                 trk_solve_update(tot, tp.damping, tp.conv_sq, passes, tp.max_passes, GSDF_EXPERIMENT(tp.debug, 1), GSDF_EXPERIMENT(tp.debug, 4), pose, &done, &converged);
                 if (trk_tr && threadIdx.x == 0) trk_tr[5] = wall_clock64() + (unsigned long long)(pose[0] != pose[0]);               /* solved */
-                if (blockIdx.x == 0 && tid == 0) {
-                    gsdf_trk_buf& o = st->trk[k & 1];
-#pragma unroll
-                    for (int i = 0; i < 7; ++i) { o.pose7[i] = pose[i]; st->pose7[i] = pose[i]; }
-                    o.done = done; o.converged = converged; o.passes = passes;
-                    /* make `done` sticky in the other parity as well: launches that the host queued beyond the
-                     * end of this optimize() must not take the older buffer for live state and redo the step
-                     * (workgroups of THIS launch that still read it return early, which is what they do anyway) */
-                    if (done) st->trk[(k - 1) & 1].done = 1;
-                    gsdf_quat_to_R(pose + 3, st->R);
-                    st->converged = converged;
-                    st->done = done;
-                    st->passes = passes;
-                    st->last_hits = tot[28];
-                    st->n_hit += (unsigned long long)tot[28];
-                    /* progress for the host's adaptive pass issue (pinned host memory, system scope) */
-                    if (tp.progress)             /* one word, so the host reads a consistent (passes, done) pair */
-                        __hip_atomic_store(&tp.progress[0], (tp.serial << 16) | (done ? 0x8000u : 0u) | (unsigned int)(passes & 0x7FFF),
-                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
+                if (blockIdx.x == 0 && tid == 0) trk_head_publish(st, k, pose, done, converged, passes, tot[28], tp.progress, tp.serial);
             }
             if (lane == 0) {
 #pragma unroll
@@ -2254,11 +2218,11 @@ __global__ __launch_bounds__(GSDF_TRACK_BLOCK, BASE ? 2 : 4) void k_track_pass(g
     for (int i = 0; i < GSDF_TRACK_NSUM; ++i) acc[i] = 0.f;
     const int xy_scale = SAMPLED ? tp.sampling : 1;
     if constexpr (BASE) {
-        if (trk_heavy) trk_gather_base<TRK_PPT>(g, tab, depth, pose, trk_pix0, 64, trk_batch, acc, xy_scale);
-        else trk_gather_base<TRK_PPT - 1>(g, tab, depth, pose, trk_pix0, 64, trk_batch, acc, xy_scale);
+        if (trk_heavy) trk_gather_base<TRK_PPT>(g, tab, depth, pose, trk_pix0, trk_batch, acc, xy_scale);
+        else trk_gather_base<TRK_PPT - 1>(g, tab, depth, pose, trk_pix0, trk_batch, acc, xy_scale);
     } else {
-        if (trk_heavy) trk_gather<TRK_PPT>(g, tab, depth, z_pre, pose, trk_pix0, 64, trk_batch, acc, trk_tr ? trk_tr + 8 + wave : nullptr, xy_scale);
-        else trk_gather<TRK_PPT - 1>(g, tab, depth, z_pre, pose, trk_pix0, 64, trk_batch, acc, trk_tr ? trk_tr + 8 + wave : nullptr, xy_scale);
+        if (trk_heavy) trk_gather<TRK_PPT>(g, tab, depth, z_pre, pose, trk_pix0, trk_batch, acc, trk_tr ? trk_tr + 8 + wave : nullptr, xy_scale);
+        else trk_gather<TRK_PPT - 1>(g, tab, depth, z_pre, pose, trk_pix0, trk_batch, acc, trk_tr ? trk_tr + 8 + wave : nullptr, xy_scale);
     }
     if (trk_tr && threadIdx.x == 0) trk_tr[2] = wall_clock64();                         /* wave 0: gather done */
     /* every wave reduces its sums as soon as its own gather is done (wsum is used here only): ONE barrier per pass tail */
@@ -2331,227 +2295,6 @@ void gsdf_launch_subsample(hipStream_t st, const float* depth, int W, int H, int
     const int Ws = (W + s - 1) / s, Hs = (H + s - 1) / s, Ns = Ws * Hs;
     hipLaunchKernelGGL(k_subsample, dim3((Ns + 255) / 256), dim3(256), 0, st, depth, W, s, Ws, Ns, out);
 }
-
-/* ------------------------------------------------------------------------------------------------
- * RigidPointOptimizer::optimize_sampled as ONE launch: k_track_all.
- *
- * The per-pass launches above pay, per Gauss-Newton pass, the launch gap (1.4 us), the head's memory round trip for the
- * group sums (1.5-2 us), the f64 atomics of the previous pass (1.5 us) and a gather from cold L2s (the per-XCD L2s are
- * invalidated at every kernel boundary).  Here the 256 workgroups (one per CU, co-resident) stay for the whole optimize():
- *  - a lane keeps the depth of its pixels in registers; voxel records and block keys stay in the XCD's L2 between passes;
- *  - the exchange of a pass uses NO atomics and NO separate flag: every workgroup stores its 29 sums as ONE ROW of ten
- *    16-byte chunks {sum, sum, sum, tag} (tag = optimize() serial and pass number; one wave instruction, agent scope) and
- *    then reads ALL rows (5 chunks per lane) until every chunk carries the tag of this pass.  A 16-byte chunk is written
- *    and read whole, so a chunk with the right tag holds the right sums: no ordering between data and flag is needed, which
- *    is what made the atomics-and-ticket variants of rounds 1-2 slower than relaunching (each ordering point is a 1.5 us
- *    round trip).  One hop: the last workgroup's store -> everybody's next poll.
- *  - every workgroup then adds the rows in the same fixed order (double), solves the 6x6 system and updates the pose:
- *    bit-identical everywhere, so no result has to be broadcast.  Rows are double-buffered by pass parity (a workgroup can
- *    be at most one pass ahead of the slowest one).
- * The wait for rows is bounded (the workgroups must be co-resident: guaranteed on an otherwise idle GPU, 256 workgroups
- * of 512 lanes on 256 CUs; another process on the same GPU can break it): a workgroup that waits longer than 50 ms raises
- * the abort word, everybody leaves, and the sticky status bit GSDF_STATUS_TRACK_ABORT makes gsdf_sync fail loudly.
- * The normals of the frame are computed by extra workgroups of the same launch, as in the per-pass path.
- * ---------------------------------------------------------------------------------------------- */
-#define TRK_ROW_CHUNKS 10                 /* 29 sums + 1 spare in chunks of 3 + tag */
-__device__ __forceinline__ gsdf_u32x4 trk_load_chunk(const gsdf_u32x4* p) {
-    gsdf_u32x4 v;
-    asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(v) : "v"(p) : "memory");
-    return v;
-}
-template <int MAXB>       /* workgroups the row exchange is sized for: a lane reads MAXB * 10 / 512 chunks per poll */
-__global__ __launch_bounds__(GSDF_TRACK_BLOCK) void k_track_all(gsdf_frame_geom g, const float* __restrict__ depth, gsdf_table tab,
-                                                                gsdf_dev_state* st, gsdf_u32x4* rows /* [2][n_track_blocks][TRK_ROW_CHUNKS] */,
-                                                                unsigned int* abort_word, gsdf_track_params tp, gsdf_normals_job nj) {
-    if ((int)blockIdx.x >= tp.n_track_blocks) {
-        extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
-        const int t = (int)blockIdx.x - tp.n_track_blocks;
-        if (t == 0 && threadIdx.x == 0) {
-            *nj.deferred_count = 0u;                            /* fresh list for the k_fuse of this frame */
-            st->frame_cur = st->frames;                         /* counter_ seen by every workgroup of k_fuse */
-        }
-        normals_tile(*reinterpret_cast<nrm_lds*>(dyn_lds), t % nj.ntx, t / nj.ntx, g.W, g.H, nj.r, nj.nc, depth, nj.nx, nj.ny, nj.nz,
-                     gsdf_tile_stats{ nj.stats, (g.W + 15) / 16, g.zmin, g.zmax });
-        return;
-    }
-    constexpr int NW = GSDF_TRACK_BLOCK / 64;
-    __shared__ float wsum[NW][32];
-    __shared__ double part[16][32];
-    /* the rows of a pass as floats, [n_track_blocks][30]: in the dynamic LDS region (the normals workgroups of this launch
-     * use the same region for their tile; static LDS would be charged to both roles and keep them from sharing a CU) */
-    extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds_t[];
-    float (*rowv)[3 * TRK_ROW_CHUNKS] = reinterpret_cast<float (*)[3 * TRK_ROW_CHUNKS]>(dyn_lds_t);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nb = tp.n_track_blocks;
-    const int n_chunks = nb * TRK_ROW_CHUNKS;
-    unsigned long long* trk_tr = nullptr;
-    if (GSDF_EXPERIMENT(tp.debug, 64) && blockIdx.x < 512u)
-        trk_tr = reinterpret_cast<unsigned long long*>(st->dbg[23]) + 16 * (2048 + (size_t)blockIdx.x);
-    /* the depth of this lane's (first) pixels: loaded once, kept across the passes */
-    float z_pre[TRK_PPT];
-    {
-        const int N = g.W * g.H, base0 = (int)blockIdx.x * GSDF_TRACK_BLOCK + tid, nthreads = nb * GSDF_TRACK_BLOCK;
-#pragma unroll
-        for (int j = 0; j < TRK_PPT; ++j) {
-            const int pix = base0 + j * nthreads;
-            z_pre[j] = pix < N ? depth[pix] : 0.f;
-        }
-    }
-    float pose[7];
-#pragma unroll
-    for (int i = 0; i < 7; ++i) pose[i] = st->pose7[i];                    /* RigidOptimizer::pose_ (kept in st->pose7 between frames) */
-    int done = 0, converged = 0, passes = 0;
-    float hits = 0.f;
-    unsigned long long hit_total = 0ull;
-    bool aborted = false;
-    for (int k = 0; k < tp.max_passes && !done; ++k) {
-        if (trk_tr && tid == 0 && k < 12) trk_tr[16 * 512 * k + 0] = wall_clock64();
-        /* ---- gather + normal-equation sums of pass k with the current pose ---- */
-        float acc[GSDF_TRACK_NSUM];
-#pragma unroll
-        for (int i = 0; i < GSDF_TRACK_NSUM; ++i) acc[i] = 0.f;
-        trk_gather<TRK_PPT>(g, tab, depth, z_pre, pose, blockIdx.x * GSDF_TRACK_BLOCK + tid, nb * GSDF_TRACK_BLOCK, TRK_PPT * nb * GSDF_TRACK_BLOCK, acc);
-        if (trk_tr && tid == 0 && k < 12) trk_tr[16 * 512 * k + 1] = wall_clock64();        /* wave 0: gather done */
-        wave_sum_to_lane63(acc);
-        if (lane == 63) {
-#pragma unroll
-            for (int i = 0; i < GSDF_TRACK_NSUM; ++i) wsum[wave][i] = acc[i];
-        }
-        __syncthreads();
-        /* ---- this workgroup's row: ten chunks {3 sums, tag}, one store instruction ---- */
-        const uint32_t tag = (tp.serial << 8) | (uint32_t)(k + 1);
-        gsdf_u32x4* buf = rows + (size_t)(k & 1) * (size_t)n_chunks;
-        if (tid < TRK_ROW_CHUNKS) {
-            float v3[3];
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                const int i = 3 * tid + q;
-                float v = 0.f;
-                if (i < GSDF_TRACK_NSUM) {
-                    v = wsum[0][i];
-#pragma unroll
-                    for (int w = 1; w < NW; ++w) v += wsum[w][i];           /* float, fixed order */
-                }
-                v3[q] = v;
-            }
-            const gsdf_u32x4 c = { __float_as_uint(v3[0]), __float_as_uint(v3[1]), __float_as_uint(v3[2]), tag };
-            gsdf_u32x4* dst = buf + (size_t)blockIdx.x * TRK_ROW_CHUNKS + tid;
-            asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(dst), "v"(c) : "memory");
-        }
-        if (trk_tr && tid == 0 && k < 12) trk_tr[16 * 512 * k + 2] = wall_clock64();        /* row stored */
-        /* ---- all rows of pass k: poll until every chunk this lane reads carries the tag ---- */
-        constexpr int PER = (MAXB * TRK_ROW_CHUNKS + GSDF_TRACK_BLOCK - 1) / GSDF_TRACK_BLOCK;   /* chunks per lane at most */
-        gsdf_u32x4 ch[PER];
-        const unsigned long long t0 = wall_clock64();
-        unsigned int rounds = 0u;
-        for (;;) {
-            bool ok = true;
-#pragma unroll
-            for (int i = 0; i < PER; ++i) {
-                const int c = tid + GSDF_TRACK_BLOCK * i;
-                ch[i] = gsdf_u32x4{ 0u, 0u, 0u, tag };
-                if (c < n_chunks) ch[i] = trk_load_chunk(buf + c);
-            }
-            /* hipcc does not track the loads issued from inline asm: each wait statement names a destination register, so
-             * no use of it can be scheduled before the data has arrived (the first wait drains all, the others cost nothing) */
-#pragma unroll
-            for (int i = 0; i < PER; ++i) asm volatile("s_waitcnt vmcnt(0)" : "+v"(ch[i]) :: "memory");
-#pragma unroll
-            for (int i = 0; i < PER; ++i) ok = ok && ch[i].w == tag;
-            ++rounds;
-            if (__syncthreads_and(ok ? 1 : 0)) break;
-            /* bounded: co-residency is a property of the launch environment, not of this code */
-            if (__hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == tp.serial || wall_clock64() - t0 > 5000000ull) {
-                aborted = true;
-                break;
-            }
-            __builtin_amdgcn_s_sleep(2);
-        }
-        if (aborted) {
-            if (tid == 0) {
-                __hip_atomic_store(abort_word, tp.serial, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                atomicOr(&st->status, GSDF_STATUS_TRACK_ABORT);
-            }
-            break;
-        }
-        if (trk_tr && tid == 0 && k < 12) { trk_tr[16 * 512 * k + 3] = wall_clock64(); trk_tr[16 * 512 * k + 6] = rounds; }   /* rows complete */
-        /* ---- the same fixed-order sum everywhere: 16 groups of rows in double, then the groups ---- */
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const int c = tid + GSDF_TRACK_BLOCK * i;
-            if (c < n_chunks) {
-                const int r = c / TRK_ROW_CHUNKS, q = c - r * TRK_ROW_CHUNKS;
-                rowv[r][3 * q] = __uint_as_float(ch[i].x); rowv[r][3 * q + 1] = __uint_as_float(ch[i].y); rowv[r][3 * q + 2] = __uint_as_float(ch[i].z);
-            }
-        }
-        __syncthreads();
-        {
-            const int v = tid & 31, grp = tid >> 5;                           /* 16 groups x 32 values */
-            const int per = (nb + 15) / 16;
-            double sgrp = 0.0;
-            if (v < 3 * TRK_ROW_CHUNKS)
-                for (int r = grp * per; r < (grp + 1) * per && r < nb; ++r) sgrp += (double)rowv[r][v];
-            part[grp][v] = sgrp;
-        }
-        __syncthreads();
-        float tot[GSDF_TRACK_NSUM];
-        {
-            double gs = 0.0;
-            if (lane < GSDF_TRACK_NSUM) {
-                gs = part[0][lane];
-#pragma unroll
-                for (int grp = 1; grp < 16; ++grp) gs += part[grp][lane];
-            }
-            const float totv = (float)gs;
-#pragma unroll
-            for (int i = 0; i < GSDF_TRACK_NSUM; ++i) tot[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(totv), i));
-        }
-        /* ---- one Gauss-Newton step (every wave of every workgroup computes it: identical bits) ---- */
-        passes = k + 1;
-        trk_solve_update(tot, tp.damping, tp.conv_sq, passes, tp.max_passes, GSDF_EXPERIMENT(tp.debug, 1), GSDF_EXPERIMENT(tp.debug, 4), pose, &done, &converged);
-        hits = tot[28];
-        hit_total += (unsigned long long)tot[28];
-        if (trk_tr && tid == 0 && k < 12) trk_tr[16 * 512 * k + 4] = wall_clock64();        /* solved */
-    }
-    if (blockIdx.x == 0 && tid == 0) {
-        if (aborted) { done = 1; converged = 0; }
-#pragma unroll
-        for (int i = 0; i < 7; ++i) st->pose7[i] = pose[i];
-        gsdf_quat_to_R(pose + 3, st->R);
-        st->converged = converged;
-        st->done = 1;
-        st->passes = passes;
-        st->last_hits = hits;
-        st->n_hit += hit_total;
-        st->trk[0].done = 1; st->trk[1].done = 1;
-        if (tp.progress)
-            __hip_atomic_store(&tp.progress[0], (tp.serial << 16) | 0x8000u | (unsigned int)(passes & 0x7FFF), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
-void gsdf_launch_track_all(hipStream_t s, const gsdf_frame_geom& g, const float* depth, gsdf_table tab, gsdf_dev_state* st,
-                           void* rows, unsigned int* abort_word, int n_blocks, const gsdf_track_params& tp_in,
-                           const gsdf_normals_job* normals) {
-    gsdf_track_params tp = tp_in;
-    tp.n_track_blocks = n_blocks;
-    gsdf_normals_job nj;
-    memset(&nj, 0, sizeof(nj));
-    int extra = 0;
-    size_t dyn = 0;
-    if (normals) {
-        nj = *normals;
-        nj.ntx = (g.W + NRM_TX - 1) / NRM_TX;
-        extra = nj.ntx * ((g.H + NRM_TY - 1) / NRM_TY);
-        dyn = sizeof(nrm_lds);
-    }
-    dyn = dyn > (size_t)n_blocks * 3 * TRK_ROW_CHUNKS * sizeof(float) ? dyn : (size_t)n_blocks * 3 * TRK_ROW_CHUNKS * sizeof(float);
-    if (n_blocks <= GSDF_TRACK_MAXBLK)
-        hipLaunchKernelGGL(k_track_all<GSDF_TRACK_MAXBLK>, dim3(n_blocks + extra), dim3(GSDF_TRACK_BLOCK), dyn, s, g, depth, tab, st,
-                           reinterpret_cast<gsdf_u32x4*>(rows), abort_word, tp, nj);
-    else
-        hipLaunchKernelGGL(k_track_all<2 * GSDF_TRACK_MAXBLK>, dim3(n_blocks + extra), dim3(GSDF_TRACK_BLOCK), dyn, s, g, depth, tab, st,
-                           reinterpret_cast<gsdf_u32x4*>(rows), abort_word, tp, nj);
-}
-size_t gsdf_track_all_rows_bytes(int n_blocks) { return (size_t)2 * (size_t)n_blocks * TRK_ROW_CHUNKS * sizeof(gsdf_u32x4); }
 
 struct pose7_arg { float p[7]; };
 __global__ void k_set_pose(gsdf_dev_state* st, pose7_arg a) {

@@ -47,10 +47,8 @@ if [ -n "${SKIP_EXTRAS:-}" ]; then ls -la $out; exit 0; fi
 python $root/tools/raycast_bench.py > $out/raycast_bench.json 2> $out/raycast_bench.err
 GRAFT_REPO_ROOT=$root bash $root/tools/raycast_pmc.sh $tag > /dev/null 2>&1
 cp $root/gpurun_out/raycast_pmc_$tag.txt $out/raycast_pmc_counters.txt 2>/dev/null
-# 5. the tracker: per-workgroup phase traces of one frame, one launch per pass (default) and the one-launch optimize() (GSDF_PERSIST=1)
-GSDF_PERSIST=0 python $root/tools/track_trace.py 20 > $out/track_trace_per_pass.txt 2>&1
-GSDF_PERSIST=1 python $root/tools/track_all_trace.py 20 > $out/track_trace_one_launch.txt 2>&1
-GSDF_PERSIST=1 python $root/bench.py --steps 20 --warmup 5 --full --only-main > $out/bench_one_launch_tracker.json 2> /dev/null
+# 5. the tracker: per-workgroup phase traces of one frame
+python $root/tools/track_trace.py 20 > $out/track_trace_per_pass.txt 2>&1
 # 6. k_fuse and the number of dispatch rounds: frame sizes with 1040 / 1200 / 1536 / 2048 tiles on the 512 workgroup slots
 for wh in "640 416" "640 480" "768 512" "1024 512"; do set -- $wh
   python $root/bench.py --steps 20 --warmup 5 --full --only-main --repeats 2 --width $1 --height $2 2>/dev/null | python -c "
