@@ -408,16 +408,12 @@ void gsdf_launch_normals(hipStream_t s, const gsdf_frame_geom& g, int win, const
  *    occupancy).  The kernel exists with two table sizes (FUSE_LCAP below), chosen per launch by the host.
  * ---------------------------------------------------------------------------------------------- */
 #define FUSE_T 16                        /* tile width */
-#ifndef FUSE_TH
-#define FUSE_TH 16                       /* tile height (a multiple of 4).  20: a 640x480 frame is 960 tiles = 1.88 dispatch rounds of the
-                                            512 workgroup slots instead of 2.34 (DESIGN.md "Dispatch rounds") */
-#endif
+#define FUSE_TH 16                       /* tile height */
 #define FUSE_ZSPLIT 2                    /* slices of the ray walk a lane pair shares: the two halves of a wave */
 #define FUSE_NWAVES (FUSE_TH / 2)        /* a wave takes 32 pixels: 16 x TH / 32 */
 #define FUSE_THREADS (64 * FUSE_NWAVES)
 #define FUSE_RP (FUSE_TH / 4)            /* row phases of the spread mapping: wave w walks rows RP * (ly & 3) + (w >> 1) */
 #define FUSE_NPASS_MAX (FUSE_NWAVES / 2) /* most bands a tile is split into (4 rows each) */
-static_assert(FUSE_TH % 4 == 0 && FUSE_TH >= 8 && FUSE_TH <= 32, "tile height");
 /* LDS table entries.  The kernel exists in two sizes (template parameter LCAP, FUSE_LCAP below is that parameter):
  *   2048  512 buckets of 4, 57 KB with the accumulators: near scenes;
  *   2560  640 buckets, 72 KB (still two workgroups per CU): keeps far tiles (2.5-3 m at 640x480 / 1 cm), which the small
@@ -425,34 +421,19 @@ static_assert(FUSE_TH % 4 == 0 && FUSE_TH >= 8 && FUSE_TH <= 32, "tile height");
  *         geometry 68 -> 63 us, of near scenes 62 -> 63 us (the bigger table clear competes with the CU's other walk).
  * The host picks per launch from what the previous fusions reported (tiles that did not fit the small table). */
 #define FUSE_LCAP LCAP
-#ifndef FUSE_LCAP_NEAR
 #define FUSE_LCAP_NEAR 2048
-#endif
-#ifndef FUSE_LCAP_FAR
 #define FUSE_LCAP_FAR 2560
-#endif
-#ifndef FUSE_POLL_SLEEP
-#define FUSE_POLL_SLEEP 8                  /* x 64 cycles between two looks at the neighbours' flags */
-#endif
-#ifndef FUSE_BSLOTS
-#define FUSE_BSLOTS 4                    /* keys per bucket of the LDS table = one ds_read_b128 per probe (2 per bucket: half the read and
-                                            compare work, 1.03 probes per sample on typical tiles -- but dense tiles then cluster: long probe
-                                            chains, 20 k samples per frame on the deferred route, 68 us instead of 61) */
-#endif
-#define FUSE_NB (FUSE_LCAP / FUSE_BSLOTS)
-/* A tile whose voxels fit uses only the first FUSE_LCAP_SMALL entries (512 buckets: the bucket index is a mask, and the flush
- * has a slot less per lane to look at); the full table is for far tiles, which would otherwise be walked in two bands */
-#define FUSE_LCAP_SMALL FUSE_LCAP_NEAR
-#define FUSE_DUAL (FUSE_LCAP == FUSE_LCAP_FAR && FUSE_LCAP_FAR != FUSE_LCAP_NEAR && FUSE_BSLOTS == 4)
+#define FUSE_POLL_SLEEP 8                /* x 64 cycles between two looks at the neighbours' flags */
+/* Buckets of the LDS table hold 4 keys = one ds_read_b128 per probe (2 per bucket: half the read and compare work, 1.03 probes
+ * per sample on typical tiles -- but dense tiles then cluster: long probe chains, 20 k samples per frame on the deferred
+ * route, 68 us instead of 61) */
+#define FUSE_NB (FUSE_LCAP / 4)
+/* In the far-size kernel a tile whose voxels fit uses only the first FUSE_LCAP_NEAR entries (512 buckets: the bucket index is a
+ * mask, and the flush has a slot less per lane to look at); the full table is for far tiles, which would otherwise be walked
+ * in two bands */
 #define FUSE_LKEY_EMPTY 0xFFFFFFFFu      /* LDS keys are 32-bit: voxel coordinates relative to the tile origin, 10 bits each */
 #define FUSE_LKEY_DEFER 0x80000000u      /* flush: the entry goes to the deferred list, low 31 bits = voxel record index */
-#define FUSE_LPROBE (48 / FUSE_BSLOTS)   /* buckets probed before a sample takes the deferred route */
-#ifndef FUSE_BOUNDS
-#define FUSE_BOUNDS __launch_bounds__(FUSE_THREADS, FUSE_OCC)
-#endif
-#ifndef FUSE_OCC
-#define FUSE_OCC (FUSE_THREADS / 128)     /* waves per SIMD the register allocation must allow: 2 workgroups per CU */
-#endif
+#define FUSE_LPROBE 12                   /* buckets probed before a sample takes the deferred route */
 /* LDS accumulators are fixed point (exact, order-independent integer adds) in THREE 64-bit words per entry, each in its
  * own array of 8-byte entries (a wave's scattered adds then use all banks; the walk is bound by LDS cycles).  Several
  * sums share a word and are added as ONE integer; the flush separates them again (a negative low field has borrowed 1
@@ -473,37 +454,11 @@ static_assert(FUSE_TH % 4 == 0 && FUSE_TH >= 8 && FUSE_TH <= 32, "tile height");
 #define FUSE_FIX_G_INV 4.76837158203125e-07f
 #define FUSE_FIX_W 16777216.0f           /* 2^24 */
 #define FUSE_FIX_W_INV 5.9604644775390625e-08f
-#ifndef FUSE_SPREAD
-#define FUSE_SPREAD 1                    /* spread lane -> (pixel, slice) mapping, see k_fuse */
-#endif
-#define FUSE_NSTAT (FUSE_SPREAD ? FUSE_NWAVES : 4) /* waves of a workgroup that hold distinct pixels */
-/* tile statistics from the normals stage (normals tiles are 32 x 16 pixels = two fusion tiles): the standard tile shape only;
- * other shapes (build experiments) reduce them from their own pixels */
-#ifndef FUSE_STATS_AHEAD
-#define FUSE_STATS_AHEAD (FUSE_T == 16 && FUSE_TH == 16)
-#endif
-/* Hand-placed wave priorities inside k_fuse (s_setprio 0..3 at the kernel's start, in front of the walk, in front of the flush):
- * build parameters for the experiment only, default none.  The library is compiled with -amdgpu-set-wave-priority, which keeps a
- * wave at priority 3 until its last batch of loads is issued (in k_fuse: up to the flush's record loads) and at 0 behind that:
- * +2 % frames/s; every hand-placed ranking of the phases on top of it lost that gain again ("Kernels"). */
-#ifndef FUSE_PRIO_START
-#define FUSE_PRIO_START -1
-#endif
-#ifndef FUSE_PRIO_WALK
-#define FUSE_PRIO_WALK -1
-#endif
-#ifndef FUSE_PRIO_FLUSH
-#define FUSE_PRIO_FLUSH -1
-#endif
-#define FUSE_SETPRIO(n) do { if ((n) >= 0) __builtin_amdgcn_s_setprio((n) < 0 ? 0 : (n)); } while (0)
 /* The flush's record accesses as LANE PAIRS: a 16-byte sc1 store is a 32-byte fabric write whatever it is next to, but two
  * adjacent lanes of ONE instruction that write the two halves of a record make one write of it (1.0x, not 2 x 0.75:
  * profiles/r03_write_calibration.txt); loads likewise.  Lanes 2j and 2j+1 therefore serve each other: instruction 1 moves the
  * even lane's record (even lane: bytes 0-15, odd lane: bytes 16-31), instruction 2 the odd lane's; the halves change lanes
- * through DPP quad permutes.  0 = every lane moves its own record with two instructions (rounds 2-4). */
-#ifndef FUSE_PAIRED_IO
-#define FUSE_PAIRED_IO 1
-#endif
+ * through DPP quad permutes. */
 template <int QP>
 __device__ __forceinline__ uint32_t fuse_quad(uint32_t v) {      /* v of the lane quad_perm QP names, all lanes active */
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, QP, 0xf, 0xf, false);
@@ -560,17 +515,12 @@ struct fuse_args {
 };
 #define FUSE_RESOLVE_INLINE 8192u       /* deferred entries the last workgroup adds itself even when a resolve launch follows */
 
-/* workgroups of fewer than 512 threads (8-row tiles, a build experiment) cannot take the normals role: the launcher then
- * computes the next frame's normals with k_normals in front of the fusion */
-#define FUSE_CARRIES_NORMALS (FUSE_THREADS >= NRM_TX * NRM_TY)
 template <int LCAP>
 struct fuse_lds {
     uint32_t key[FUSE_LCAP] __attribute__((aligned(16)));
     unsigned long long acc[3][FUSE_LCAP] __attribute__((aligned(16)));  /* see above: s | w + gz | gx + gy */
     unsigned int cnt[2][FUSE_NWAVES];       /* per wave: samples with w > 0, valid pixels */
     unsigned int n_defer, defer_base;
-    unsigned int st_min[FUSE_NSTAT], st_max[FUSE_NSTAT];  /* per wave: smallest / largest valid depth (float bits) */
-    float st_cnt[FUSE_NSTAT];                             /* per wave: valid pixels */
     int dec[8];                         /* the tile-wide decisions, made by wave 0: n_pass, big, ox, oy, oz, range_ok */
     unsigned int ordered;               /* flush with plain read-modify-write (1) or through the deferred list (0) */
     unsigned int any_defer, is_last;    /* this workgroup appended to the deferred list / is the last one to finish */
@@ -955,13 +905,15 @@ __device__ __forceinline__ void fuse_head(const fuse_args& a, int tid, bool solv
  * wait expires performs the head itself (bit-identical).  If optimize() has not ended with that head, every workgroup leaves,
  * and the host's next batch starts with a tracker launch that skips its head (gsdf_track_params::head_done). */
 template <int LCAP, bool NEXT_NORMALS, bool HEAD>
-__global__ FUSE_BOUNDS void k_fuse(fuse_args a) {
+__global__ __launch_bounds__(FUSE_THREADS, FUSE_THREADS / 128)  /* waves per SIMD the register allocation must allow: 2 workgroups per CU */
+void k_fuse(fuse_args a) {
+    constexpr bool DUAL = LCAP == FUSE_LCAP_FAR;               /* the far-size kernel: near tiles use the first FUSE_LCAP_NEAR entries */
     __shared__ fuse_lds<LCAP> L;
     const int tid = threadIdx.x;
-    FUSE_SETPRIO(FUSE_PRIO_START);
-    if constexpr (NEXT_NORMALS && FUSE_CARRIES_NORMALS) {
+    if constexpr (NEXT_NORMALS) {
     if ((int)blockIdx.x >= a.n_tiles) {                       /* the next frame's normals, in the tail of this launch */
         static_assert(sizeof(nrm_lds) <= sizeof(fuse_lds<LCAP>), "the normals tile works in the fusion table's LDS");
+        static_assert(FUSE_THREADS >= NRM_TX * NRM_TY, "a fusion workgroup has a thread per pixel of the normals tile");
         const int t = (int)blockIdx.x - a.n_tiles;
         if (a.use_dev_pose) {
             /* a tracked frame (gsdf_hint_next_depth_dev): only beside a fusion that RUNS -- there the tail is idle; a launch whose
@@ -1034,11 +986,8 @@ __global__ FUSE_BOUNDS void k_fuse(fuse_args a) {
     const gsdf_frame_geom& g = a.g;
     const long long frame_cur = a.vis ? a.st->frame_cur : 0;   /* Sdf::counter_ of this update (snapshot by k_normals) */
     const int wave = tid >> 6, lane = tid & 63;
-    const int zslice = wave >> 2;
-    (void)zslice;
     const int lx = lane & 7, ly = lane >> 3;
     const int tile_x = (int)(tile_id & 0xFFFFu), tile_y = (int)(tile_id >> 16);
-#if FUSE_STATS_AHEAD
     /* The tile's depth range and its number of valid pixels come from the normals stage of this frame (gsdf_tile_stats): three
      * words, requested now.  Wave 0 makes the tile-wide decisions from them while the seven pixel planes are still on their way
      * -- they used to be reduced from the arrived pixels (DPP, LDS, a barrier) and the decisions (~200 dependent instructions
@@ -1046,7 +995,6 @@ __global__ FUSE_BOUNDS void k_fuse(fuse_args a) {
      * together (the first dispatch round) or run alone (the last). */
     const uint32_t* tsr = a.tile_stats + 4 * ((size_t)tile_y * a.ntx + tile_x);
     const unsigned int ts_zmin = tsr[0], ts_zmax = tsr[1], ts_nval = tsr[2];
-#endif
     bool valid = false;
     float z = 0.f;
     gsdf_v3 Rxy = { 0.f, 0.f, 0.f }, Rn = { 0.f, 0.f, 0.f };   /* Rn carries the fixed-point scale: w * Rn is the scaled term */
@@ -1076,16 +1024,11 @@ __global__ FUSE_BOUNDS void k_fuse(fuse_args a) {
     };
     /* the common case is one band: its pixels are requested now; the table clear and everything of the tile-wide
      * decisions that does not depend on the pixels (corner rays of the tile's frustum) run while the loads are in flight */
-#if FUSE_SPREAD
     /* Lanes of a wave are spread out, because lanes that hit the same voxel in one instruction serialise in the LDS
      * atomics: a wave takes 32 pixels (every 2nd in x, every (4 / bands)-th in y: wave w has phase (w & 1, w >> 1)) and
      * BOTH slices of their ray walk (lanes 0-31 / 32-63), so neighbouring lanes are >= 2 pixels or half a ray apart. */
     static_assert(FUSE_ZSPLIT == 2, "the spread mapping splits a ray between the two halves of a wave");
     const int px0 = tile_x * FUSE_T + 2 * lx + (wave & 1), py0 = tile_y * FUSE_TH + FUSE_RP * (ly & 3) + (wave >> 1);
-#else
-    static_assert(FUSE_TH == 16, "the compact mapping exists for 16 x 16 tiles only");
-    const int px0 = tile_x * FUSE_T + (wave & 1) * 8 + lx, py0 = tile_y * FUSE_T + ((wave >> 1) & 1) * 8 + ly;
-#endif
     float raw[7] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
     const bool inside0 = px0 < g.W && py0 < g.H;
     if (inside0) {
@@ -1116,20 +1059,6 @@ __global__ FUSE_BOUNDS void k_fuse(fuse_args a) {
             dmax[0] = fmaxf(dmax[0], d.x); dmax[1] = fmaxf(dmax[1], d.y); dmax[2] = fmaxf(dmax[2], d.z);
         }
     }
-#if !FUSE_STATS_AHEAD
-    if (GSDF_EXPERIMENT(a.debug, 64)) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); GSDF_TRACE(a, tr, 11); }   /* pixel loads arrived */
-    finish_pixel(inside0, raw[0], raw[1], raw[2], raw[3], raw[4], raw[5], raw[6]);
-    /* depth range of the tile and the number of valid pixels: one entry per wave that holds distinct pixels */
-    if (FUSE_SPREAD || zslice == 0) {
-        unsigned int zb = valid ? __float_as_uint(z) : 0x7F800000u, zt = valid ? __float_as_uint(z) : 0u;
-        wave_uminmax(zb, zt);                                         /* DPP: no LDS round trips */
-        /* spread mapping: both halves of a wave hold the same 32 pixels */
-        const float cnt = (float)__popcll(FUSE_SPREAD ? (__ballot(valid) & 0xFFFFFFFFull) : __ballot(valid));
-        if (lane == 0) { L.st_min[wave] = zb; L.st_max[wave] = zt; L.st_cnt[wave] = cnt; }
-    }
-    __syncthreads();
-    GSDF_TRACE(a, tr, 12);                                            /* tile statistics reduced */
-#endif
     const int nk_all = 2 * g.factor + 1;
     const int colour = (tile_x & 1) + 2 * (tile_y & 1);
     /* Wave 0 derives the tile-wide decisions from the per-wave entries and hands them to the others through LDS: ~200 uniform
@@ -1139,18 +1068,8 @@ __global__ FUSE_BOUNDS void k_fuse(fuse_args a) {
     int ox = 0, oy = 0, oz = 0;
     bool range_ok = false;
     if (wave == 0) {
-#if FUSE_STATS_AHEAD
         const unsigned int zmin_bits = ts_zmin, zmax_bits = ts_zmax;
         const float n_valid = (float)ts_nval;
-#else
-        unsigned int zmin_bits = L.st_min[0], zmax_bits = L.st_max[0];
-        float n_valid = L.st_cnt[0];
-#pragma unroll
-        for (int i = 1; i < FUSE_NSTAT; ++i) {
-            zmin_bits = min(zmin_bits, L.st_min[i]); zmax_bits = max(zmax_bits, L.st_max[i]);
-            n_valid += L.st_cnt[i];                                   /* small integers: exact in any order */
-        }
-#endif
         /* (1) of the flush comment below: may this tile write its voxels itself? */
         const float D = 1.7421f * g.vs;
         const float s_min = __uint_as_float(zmin_bits) - (float)g.factor * g.vs - 2.f * D;
@@ -1183,10 +1102,10 @@ __global__ FUSE_BOUNDS void k_fuse(fuse_args a) {
         /* a tile without a valid pixel (background: two thirds of the tiles of a sphere frame) walks and flushes nothing: no band
          * at all -- it used to go through an empty walk and an empty flush, ~7 us of a workgroup slot */
         if (!(n_valid > 0.f)) n_pass = 0;
-        big = FUSE_DUAL ? (est > 0.8f * FUSE_LCAP_SMALL * (float)n_pass ? 1 : 0) : 0;
+        big = DUAL ? (est > 0.8f * FUSE_LCAP_NEAR * (float)n_pass ? 1 : 0) : 0;
         big = __builtin_amdgcn_readfirstlane(big);
         /* tiles the small table cannot hold in one band: what the host chooses the next launches' table size by */
-        if (tid == 0 && est > 0.8f * FUSE_LCAP_SMALL) atomicAdd(&a.st->far_tiles, 1u);
+        if (tid == 0 && est > 0.8f * FUSE_LCAP_NEAR) atomicAdd(&a.st->far_tiles, 1u);
         n_pass = __builtin_amdgcn_readfirstlane(n_pass);
         /* origin of the tile-local voxel coordinates: the world bounding box of the tile's frustum chunk
          * (4 corner rays x the two ends of the sampled depth range) minus a margin; a sample whose voxel is not
@@ -1209,12 +1128,10 @@ __global__ FUSE_BOUNDS void k_fuse(fuse_args a) {
                    oz >= -GSDF_KEY_OFF && oz + 1023 < GSDF_KEY_OFF;
         if (lane == 0) { L.dec[0] = n_pass; L.dec[1] = big; L.dec[2] = ox; L.dec[3] = oy; L.dec[4] = oz; L.dec[5] = range_ok ? 1 : 0; }
     }
-#if FUSE_STATS_AHEAD
     /* (wave 0 has decided while the loads were in flight; now everybody takes its pixel) */
     if (GSDF_EXPERIMENT(a.debug, 64)) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); GSDF_TRACE(a, tr, 11); }   /* (wave 0: decisions made and) pixel loads arrived */
     finish_pixel(inside0, raw[0], raw[1], raw[2], raw[3], raw[4], raw[5], raw[6]);
     GSDF_TRACE(a, tr, 12);
-#endif
     __syncthreads();
     n_pass = __builtin_amdgcn_readfirstlane(L.dec[0]); big = __builtin_amdgcn_readfirstlane(L.dec[1]);
     ox = __builtin_amdgcn_readfirstlane(L.dec[2]); oy = __builtin_amdgcn_readfirstlane(L.dec[3]); oz = __builtin_amdgcn_readfirstlane(L.dec[4]);
@@ -1227,22 +1144,16 @@ __global__ FUSE_BOUNDS void k_fuse(fuse_args a) {
     for (int pass = 0; pass < n_pass; ++pass) {
     /* lanes -> (pixel of the band, slice of the ray walk).  One band: as loaded above, FUSE_ZSPLIT slices.  Two bands
      * of 16x8 pixels: 2 waves (8x8 each) per slice, twice the slices.  Four bands of 16x4: 1 wave per slice. */
-#if FUSE_SPREAD
     /* a band of 256 / n_pass pixels = G groups of 32 (one per wave % G), walked in 2 * n_pass slices: the two halves
      * of a wave take slices 2 (wave / G) and 2 (wave / G) + 1 */
-    const int G = FUSE_NWAVES / n_pass, grp = wave % G;              /* n_pass is 1, 2 or FUSE_NPASS_MAX */
+    const int G = FUSE_NWAVES / n_pass, grp = wave % G;              /* n_pass is 1, 2 or 4 of 8 waves: G is 8, 4 or 2, never odd */
     const int zs = (lane >> 5) + 2 * (wave / G);
     int bx = 2 * lx + (grp & 1), by = (G / 2) * (ly & 3) + (grp >> 1);
-    if (G & 1) {                                                      /* an odd number of groups (TH = 20, two bands): row-major pixels */
+    /* never taken, and kept: without it the test build's k_fuse<2048,false,true> spills 59 SGPRs instead of 45 (LABNOTES, "k_fuse: one build") */
+    if (G & 1) {
         const int q = grp * 32 + (lane & 31);
         bx = q & (FUSE_T - 1); by = q / FUSE_T;
     }
-#else
-    const int per = FUSE_THREADS / (FUSE_ZSPLIT * n_pass);
-    const int q = tid % per, zs = tid / per;
-    const int bx = n_pass == 4 ? (q & 15) : ((q >> 6) & 1) * 8 + (q & 7);
-    const int by = n_pass == 4 ? (q >> 4) : (q >> 7) * 8 + ((q >> 3) & 7);
-#endif
     if (n_pass > 1)
         load_pixel(tile_x * FUSE_T + bx, tile_y * FUSE_TH + pass * (FUSE_TH / n_pass) + by,
                    L.plane[0], L.plane[1], L.plane[2], L.plane[3], L.plane[4], L.plane[5], L.plane[6]);
@@ -1252,18 +1163,15 @@ __global__ FUSE_BOUNDS void k_fuse(fuse_args a) {
     const int k_hi = -g.factor + ((zs + 1) * nk_all) / (FUSE_ZSPLIT * n_pass) - 1;
     const int nk_lane = k_hi - k_lo + 1;
     int nk = nk_lane;                                                  /* loop count of the wave: its longest slice */
-#if FUSE_SPREAD
     nk = max(nk, __shfl_xor(nk, 32));
-#endif
     nk = __builtin_amdgcn_readfirstlane(nk);
-    FUSE_SETPRIO(FUSE_PRIO_WALK);                    /* (build experiment, default none: see FUSE_PRIO_*) */
     if (nk > 0 && __any(valid)) {                    /* waves without any valid pixel skip the walk */
         /* One sample per lane and iteration (2, 3, 4 or 6 samples in flight were measured slower: registers).  The loop
          * is bound by VALU issue when both workgroups of a CU walk, so it is written for instruction count: x and y go
          * through packed (2 x f32) instructions, the clamp is one v_med3, keys / hash / LDS addresses use shift-adds and
          * 24-bit multiply-adds (v_mul_lo_u32 is quarter rate), the weight goes to fixed point without the double trick. */
         const gsdf_f2 Rxy2 = { Rxy.x, Rxy.y }, t2 = { t[0], t[1] }, Rz2 = { R[2], R[5] }, Rn2 = { Rn.x, Rn.y };
-        const uint32_t nb_used = (FUSE_DUAL && !big) ? (uint32_t)(FUSE_LCAP_SMALL / FUSE_BSLOTS) : (uint32_t)FUSE_NB;   /* buckets of this tile's table */
+        const uint32_t nb_used = (DUAL && !big) ? (uint32_t)(FUSE_LCAP_NEAR / 4) : (uint32_t)FUSE_NB;   /* buckets of this tile's table */
         float kf = (float)k_lo;                                       /* small integers: exact */
         for (int c0 = 0; c0 < nk; ++c0, kf += 1.f) {
             /* 1. the sample */
@@ -1294,54 +1202,30 @@ __global__ FUSE_BOUNDS void k_fuse(fuse_args a) {
              * (best 3-D lattice for this modulus, found by search), so buckets fill evenly, rarely
              * overflow, and the distinct voxels of one wave instruction never compete for a bucket: counted on
              * tiles of the bench stream, 1.004 probes per sample.  (The HBM table keeps the full 64-bit finaliser.) */
-            static_assert((FUSE_BSLOTS == 2 && FUSE_NB == 1024) || (FUSE_BSLOTS == 4 && (FUSE_NB == 512 || FUSE_NB == 480 || FUSE_NB == 640 || FUSE_NB == 256 || FUSE_NB == 320)),
-                          "lattice constants exist for 1024 x 2, 512 x 4, 480 x 4, 640 x 4 (16-row tiles) and 256 x 4, 320 x 4 (8-row tiles)");
+            static_assert(FUSE_NB == 512 || FUSE_NB == 640, "lattice constants exist for 512 x 4 and 640 x 4");
             uint32_t bk;
-            if (FUSE_BSLOTS == 2) bk = gsdf_mad_u24(lz3, 75u, gsdf_mad_u24(ly3, 86u, lx3)) & 1023u;
-            else if (FUSE_NB == 640 && (big || !FUSE_DUAL)) {          /* x + 253 y + 541 z (mod 640): min distance 9.3; 1.000 probes per sample on the densest tiles */
+            if (DUAL && big) {                                          /* x + 253 y + 541 z (mod 640): min distance 9.3; 1.000 probes per sample on the densest tiles */
                 const uint32_t hx = gsdf_mad_u24(lz3, 541u, gsdf_mad_u24(ly3, 253u, lx3));         /* < 2^20 for local keys */
                 bk = hx - 640u * __umulhi(hx, 6710887u);                /* exact for hx < 2^21 */
                 bk = bk < 640u ? bk : 0u;                               /* keys outside the local range: any bucket, never used */
             }
-            else if (FUSE_NB == 320 && (big || !FUSE_DUAL)) {          /* x + 299 y + 271 z (mod 320): min distance 7.3 (8-row tiles, far) */
-                const uint32_t hx = gsdf_mad_u24(lz3, 271u, gsdf_mad_u24(ly3, 299u, lx3));         /* < 2^20 for local keys */
-                bk = hx - 320u * __umulhi(hx, 13421773u);               /* exact for hx < 2^25 */
-                bk = bk < 320u ? bk : 0u;
-            }
-            else if (FUSE_NB == 480) {                                 /* x + 313 y + 195 z (mod 480): min distance 8.1; 1.12 probes per sample on the densest tiles */
-                const uint32_t hx = gsdf_mad_u24(lz3, 195u, gsdf_mad_u24(ly3, 313u, lx3));         /* < 2^20 for local keys */
-                bk = hx - 480u * __umulhi(hx, 8947849u);                /* exact for hx < 2^20 */
-                bk = bk < 480u ? bk : 0u;                               /* keys outside the local range: any bucket, never used */
-            }
-            else if (FUSE_LCAP_SMALL == 1024) bk = gsdf_mad_u24(lz3, 73u, gsdf_mad_u24(ly3, 136u, lx3)) & 255u;   /* x + 136 y + 73 z (mod 256): min distance 6.9 (8-row tiles) */
             else bk = gsdf_mad_u24(lz3, 143u, gsdf_mad_u24(ly3, 98u, lx3)) & 511u;
             /* 2.-4. look the voxel up in the LDS table: one read per bucket; the first slot that holds the key or is empty
              *    decides (used slots are a prefix: entries are never removed and inserts take the first empty slot), at
              *    most one CAS per probe.  Plain LDS reads: a stale EMPTY is resolved by the CAS. */
             int slot = -1;
             bool pend = act && local && !GSDF_EXPERIMENT(a.debug, 2);
-            if (GSDF_EXPERIMENT(a.debug, 32)) { if (act) slot = (int)(FUSE_BSLOTS * bk + (key & (FUSE_BSLOTS - 1))); pend = false; }   /* experiment: no lookup */
+            if (GSDF_EXPERIMENT(a.debug, 32)) { if (act) slot = (int)(4 * bk + (key & 3)); pend = false; }   /* experiment: no lookup */
             for (int probe = 0; probe < FUSE_LPROBE && pend; ++probe) {       /* a divergent loop: lanes leave it as they find their slot */
                 ++dbg_go;
-                int pos;
-                bool hit;
-                if (FUSE_BSLOTS == 2) {
-                    const uint2 k2 = *reinterpret_cast<const uint2*>(&L.key[2 * bk]);
-                    const bool h0 = k2.x == key, h1 = k2.y == key;
-                    const bool m0 = h0 | (k2.x == FUSE_LKEY_EMPTY), m1 = h1 | (k2.y == FUSE_LKEY_EMPTY);
-                    pos = m1 ? 1 : -1;
-                    pos = m0 ? 0 : pos;
-                    hit = h0 | h1;
-                } else {
-                    const uint4 k4 = *reinterpret_cast<const uint4*>(&L.key[4 * bk]);
-                    const bool h0 = k4.x == key, h1 = k4.y == key, h2 = k4.z == key, h3 = k4.w == key;
-                    const bool m0 = h0 | (k4.x == FUSE_LKEY_EMPTY), m1 = h1 | (k4.y == FUSE_LKEY_EMPTY),
-                               m2 = h2 | (k4.z == FUSE_LKEY_EMPTY), m3 = h3 | (k4.w == FUSE_LKEY_EMPTY);
-                    pos = m3 ? 3 : -1;
-                    pos = m2 ? 2 : pos; pos = m1 ? 1 : pos; pos = m0 ? 0 : pos;
-                    hit = h0 | h1 | h2 | h3;
-                }
-                const int at = (int)((uint32_t)FUSE_BSLOTS * bk) + pos;
+                const uint4 k4 = *reinterpret_cast<const uint4*>(&L.key[4 * bk]);
+                const bool h0 = k4.x == key, h1 = k4.y == key, h2 = k4.z == key, h3 = k4.w == key;
+                const bool m0 = h0 | (k4.x == FUSE_LKEY_EMPTY), m1 = h1 | (k4.y == FUSE_LKEY_EMPTY),
+                           m2 = h2 | (k4.z == FUSE_LKEY_EMPTY), m3 = h3 | (k4.w == FUSE_LKEY_EMPTY);
+                int pos = m3 ? 3 : -1;
+                pos = m2 ? 2 : pos; pos = m1 ? 1 : pos; pos = m0 ? 0 : pos;
+                const bool hit = h0 | h1 | h2 | h3;
+                const int at = (int)(4u * bk) + pos;
                 const bool try_cas = pend && !hit && pos >= 0;
                 if (pend && hit) { slot = at; pend = false; }
                 if (pend && pos < 0) bk = bk + 1u == nb_used ? 0u : bk + 1u;                                 /* bucket full of others */
@@ -1380,7 +1264,6 @@ __global__ FUSE_BOUNDS void k_fuse(fuse_args a) {
             }
         }
     }
-    FUSE_SETPRIO(FUSE_PRIO_FLUSH);                   /* (build experiment, default none) */
     if (GSDF_EXPERIMENT(a.debug, 128) && lane == 0) {
         atomicAdd(&a.st->n_hit, (unsigned long long)dbg_go);
         atomicAdd(&a.st->dbg[0], (unsigned long long)dbg_full); atomicAdd(&a.st->dbg[1], (unsigned long long)dbg_lost);
@@ -1422,7 +1305,7 @@ __global__ FUSE_BOUNDS void k_fuse(fuse_args a) {
         for (int e = 0; e < NE; ++e) {
             /* back from the tile-local key to the packed voxel key of the HBM map */
             const int i = tid + FUSE_THREADS * e;
-            const uint32_t lk = (i < FUSE_LCAP && (big || !FUSE_DUAL || i < FUSE_LCAP_SMALL)) ? L.key[i] : FUSE_LKEY_EMPTY;
+            const uint32_t lk = (i < FUSE_LCAP && (big || !DUAL || i < FUSE_LCAP_NEAR)) ? L.key[i] : FUSE_LKEY_EMPTY;
             const unsigned long long ek = gsdf_key_pack(ox + (int)(lk & 1023u), oy + (int)((lk >> 10) & 1023u), oz + (int)(lk >> 20));
             bkey[e] = gsdf_block_key(ek);
             home[e] = gsdf_hash(bkey[e]) & tab.block_mask;
@@ -1498,7 +1381,7 @@ __global__ FUSE_BOUNDS void k_fuse(fuse_args a) {
              * should look at the ISA again or issue loads and wait as ONE asm statement, as that patch does. */
             gsdf_u32x4 ra[NE], rb[NE];
             /* (the 2560-entry table with the normals role is at the register limit: its five entries per lane stay unpaired) */
-            constexpr bool PAIRED = FUSE_PAIRED_IO && !(NE > 4 && NEXT_NORMALS);
+            constexpr bool PAIRED = !(NE > 4 && NEXT_NORMALS);
             /* ra[e]: the half this lane moves of the EVEN lane's record of entry e (even lane: bytes 0-15, odd lane: 16-31),
              * rb[e]: its half of the ODD lane's record.  The exchanges run with all lanes active; only the memory instructions
              * are predicated (a pair moves a record if the lane that owns it has one). */
@@ -1750,25 +1633,20 @@ void gsdf_launch_fuse(hipStream_t s, const gsdf_fuse_launch& f) {
     a.n_tiles = n;
     a.nrm_depth = f.next_depth; a.nrm_x = f.next_nx; a.nrm_y = f.next_ny; a.nrm_z = f.next_nz;
     a.nrm_r = f.win / 2; a.nrm_ntx = (f.g.W + NRM_TX - 1) / NRM_TX;
-    int extra = f.next_depth ? a.nrm_ntx * ((f.g.H + NRM_TY - 1) / NRM_TY) : 0;
-    if (extra && !FUSE_CARRIES_NORMALS) {
-        gsdf_launch_normals(s, f.g, f.win, f.nc, f.next_depth, f.next_nx, f.next_ny, f.next_nz, nullptr, nullptr, f.next_tile_stats);
-        extra = 0;
-    }
+    const int extra = f.next_depth ? a.nrm_ntx * ((f.g.H + NRM_TY - 1) / NRM_TY) : 0;
     std::memset(&a.hd, 0, sizeof(a.hd));
     a.nrm_token = f.next_token;
-    if (f.head && f.use_dev_pose && f.head->k > 0) {
-        a.hd = *f.head;
-        if (extra) {
-            if (f.far_table) hipLaunchKernelGGL((k_fuse<FUSE_LCAP_FAR, true, true>), dim3(n + extra), dim3(FUSE_THREADS), 0, s, a);
-            else hipLaunchKernelGGL((k_fuse<FUSE_LCAP_NEAR, true, true>), dim3(n + extra), dim3(FUSE_THREADS), 0, s, a);
-        } else if (f.far_table) hipLaunchKernelGGL((k_fuse<FUSE_LCAP_FAR, false, true>), dim3(n), dim3(FUSE_THREADS), 0, s, a);
-        else hipLaunchKernelGGL((k_fuse<FUSE_LCAP_NEAR, false, true>), dim3(n), dim3(FUSE_THREADS), 0, s, a);
-    } else if (extra) {
-        if (f.far_table) hipLaunchKernelGGL((k_fuse<FUSE_LCAP_FAR, true, false>), dim3(n + extra), dim3(FUSE_THREADS), 0, s, a);
-        else hipLaunchKernelGGL((k_fuse<FUSE_LCAP_NEAR, true, false>), dim3(n + extra), dim3(FUSE_THREADS), 0, s, a);
-    } else if (f.far_table) hipLaunchKernelGGL((k_fuse<FUSE_LCAP_FAR, false, false>), dim3(n), dim3(FUSE_THREADS), 0, s, a);
-    else hipLaunchKernelGGL((k_fuse<FUSE_LCAP_NEAR, false, false>), dim3(n), dim3(FUSE_THREADS), GSDF_EXPERIMENT(f.debug, 4096) ? 81920 : 0, s, a);   /* experiment: 1 workgroup per CU */
+    const bool head = f.head && f.use_dev_pose && f.head->k > 0;
+    if (head) a.hd = *f.head;
+    /* the eight instantiations: table size x normals role (its workgroups behind the tiles) x head */
+    void (*const kern[2][2][2])(fuse_args) = {
+        { { k_fuse<FUSE_LCAP_NEAR, false, false>, k_fuse<FUSE_LCAP_NEAR, false, true> },
+          { k_fuse<FUSE_LCAP_NEAR, true, false>, k_fuse<FUSE_LCAP_NEAR, true, true> } },
+        { { k_fuse<FUSE_LCAP_FAR, false, false>, k_fuse<FUSE_LCAP_FAR, false, true> },
+          { k_fuse<FUSE_LCAP_FAR, true, false>, k_fuse<FUSE_LCAP_FAR, true, true> } } };
+    /* experiment: 1 workgroup per CU (the plain near launch only) */
+    const size_t dyn_lds = (!f.far_table && !extra && !head && GSDF_EXPERIMENT(f.debug, 4096)) ? 81920 : 0;
+    hipLaunchKernelGGL(kern[f.far_table ? 1 : 0][extra ? 1 : 0][head ? 1 : 0], dim3(n + extra), dim3(FUSE_THREADS), dyn_lds, s, a);
     if (f.resolve_follows)
         hipLaunchKernelGGL(k_fuse_resolve, dim3(512), dim3(256), 0, s, f.deferred, f.deferred_count, f.deferred_cap, gate, f.st, f.ticket + 1);
 }
@@ -1820,12 +1698,9 @@ __global__ void k_track_none(gsdf_dev_state* st) {
 }
 void gsdf_launch_track_none(hipStream_t s, gsdf_dev_state* st) { hipLaunchKernelGGL(k_track_none, dim3(1), dim3(64), 0, s, st); }
 
-#ifndef TRK_PPT
 #define TRK_PPT 3          /* pixels per lane handled as one batch: independent gathers in flight */
-#endif
-#ifndef TRK_CHUNK          /* pixels of one workgroup's batch in k_track_pass: half of its waves TRK_PPT per lane, the others one less */
+/* pixels of one workgroup's batch in k_track_pass: half of its waves TRK_PPT per lane, the others one less */
 #define TRK_CHUNK ((GSDF_TRACK_BLOCK / 128) * 64 * (2 * TRK_PPT - 1))
-#endif
 
 /* Gather + normal-equation sums of one pass for this lane's pixels: back-project, voxel lookup (block key from the
  * L2-resident key array, then the 32-byte record), residual, Jacobian.  The lane's pixels of one batch are pix0 + j * 64

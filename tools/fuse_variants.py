@@ -1,4 +1,4 @@
-"""A/B of fusion-kernel variants (tools/build_variant.sh): GT-pose fusion of the S-tum stream through each library,
+"""A/B of two (or more) builds of the library, e.g. parent and branch: GT-pose fusion of the S-tum stream through each library,
 time per fusion (HIP events around k_fuse + k_fuse_resolve, and wall clock per frame incl. k_normals) and the
 fused map compared with the first library's (keys identical, sums within float noise).
 usage: python tools/fuse_variants.py [--frames N] [--size WxH] [--vs 0.01] [--cap 22] lib1.so lib2.so ..."""

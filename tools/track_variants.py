@@ -1,5 +1,5 @@
-"""A/B of library variants on the tracked S-tum stream (the bench loop): frames/s, tracker passes, per-launch HIP-event
-times of the three kernel groups, and the final pose of every variant against the first one's.
+"""A/B of two (or more) builds of the library, e.g. parent and branch, on the tracked S-tum stream (the bench loop): frames/s,
+tracker passes, per-launch HIP-event times of the three kernel groups, and the final pose of every build against the first one's.
 usage: python tools/track_variants.py [--frames N] lib1.so lib2.so ..."""
 import argparse, os, sys, time
 import numpy as np
