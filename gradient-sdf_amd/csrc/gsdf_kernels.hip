@@ -1158,6 +1158,11 @@ void k_fuse(fuse_args a) {
         load_pixel(tile_x * FUSE_T + bx, tile_y * FUSE_TH + pass * (FUSE_TH / n_pass) + by,
                    L.plane[0], L.plane[1], L.plane[2], L.plane[3], L.plane[4], L.plane[5], L.plane[6]);
     n_val_w += (unsigned int)__popcll(__ballot(valid && zs == 0));    /* every pixel is held by one lane per slice */
+    /* A pixel whose normal is not finite (the window of a denormal depth, a singular window) passes the reference's gates -- they
+     * are `<` comparisons -- and is fused: distance and weight as ever, the gradient sum of its voxels NaN.  The fixed-point
+     * accumulators have no NaN, so such a pixel stays out of the walk below and takes the float route behind it. */
+    const bool nan_normal = valid && !(fabsf(Rn.x) + fabsf(Rn.y) + fabsf(Rn.z) < __builtin_inff());
+    const bool walk = valid && !nan_normal;
     /* this slice's share of the ray walk k = -factor..factor (:101); the order is free (sums) */
     const int k_lo = -g.factor + (zs * nk_all) / (FUSE_ZSPLIT * n_pass);
     const int k_hi = -g.factor + ((zs + 1) * nk_all) / (FUSE_ZSPLIT * n_pass) - 1;
@@ -1165,7 +1170,7 @@ void k_fuse(fuse_args a) {
     int nk = nk_lane;                                                  /* loop count of the wave: its longest slice */
     nk = max(nk, __shfl_xor(nk, 32));
     nk = __builtin_amdgcn_readfirstlane(nk);
-    if (nk > 0 && __any(valid)) {                    /* waves without any valid pixel skip the walk */
+    if (nk > 0 && __any(walk)) {                     /* waves without any walkable pixel skip the walk */
         /* One sample per lane and iteration (2, 3, 4 or 6 samples in flight were measured slower: registers).  The loop
          * is bound by VALU issue when both workgroups of a CU walk, so it is written for instruction count: x and y go
          * through packed (2 x f32) instructions, the clamp is one v_med3, keys / hash / LDS addresses use shift-adds and
@@ -1191,7 +1196,7 @@ void k_fuse(fuse_args a) {
             const float sdf = pc_z - z;                                /* :106 */
             /* :107 Sdf::weight: 1 for sdf <= 0 (there 1 - sdf / T >= 1), the ramp up to T, 0 beyond (and for NaN) */
             const float w = sdf <= g.T ? __builtin_amdgcn_fmed3f(1.f - sdf * g.inv_T, -__builtin_inff(), 1.f) : 0.f;
-            const bool act = valid && w > 0.f && c0 < nk_lane;
+            const bool act = walk && w > 0.f && c0 < nk_lane;
             n_upd_w += (unsigned int)__popcll(__ballot(act));
             /* tile-local key: 10 bits per axis relative to the tile origin */
             const uint32_t lx3 = (uint32_t)(vx - ox), ly3 = (uint32_t)(vy - oy), lz3 = (uint32_t)(vz - oz);
@@ -1262,6 +1267,35 @@ void k_fuse(fuse_args a) {
                     vis_mark(a, p, frame_cur);
                 }
             }
+        }
+    }
+    if (nk > 0 && __any(nan_normal)) {
+        /* the same samples, one by one through the deferred list: weight and distance sum take the fixed-point rounding of every
+         * other sample, the gradient term is the float product and carries the NaN into k_fuse_resolve's float atomics.
+         * KEEP IN STEP with "1. the sample" of the walk above: position, float2vox, sdf and weight (:103-:107) are the same
+         * operations in scalar form (the walk's packed x / y forms round identically under -ffp-contract=off); a change there
+         * belongs here as well -- tests/test_gpu_input_edges.py compares this route with the oracle voxel by voxel. */
+        float kf = (float)k_lo;
+        for (int c0 = 0; c0 < nk; ++c0, kf += 1.f) {
+            const float sd = z + kf * g.vs;
+            const float px = sd * Rxy.x + t[0], py = sd * Rxy.y + t[1], pzw = sd * Rxy.z + t[2];      /* :103 */
+            const float rx = gsdf_roundf(g.inv_vs * px), ry = gsdf_roundf(g.inv_vs * py), rz = gsdf_roundf(g.inv_vs * pzw);   /* :104 */
+            const int vx = (int)rx, vy = (int)ry, vz = (int)rz;
+            const float pc_z = gsdf_sum3(R[2] * (g.vs * rx - t[0]), R[5] * (g.vs * ry - t[1]), R[8] * (g.vs * rz - t[2]));     /* :105 */
+            const float sdf = pc_z - z;                                /* :106 */
+            const float w = sdf <= g.T ? __builtin_amdgcn_fmed3f(1.f - sdf * g.inv_T, -__builtin_inff(), 1.f) : 0.f;
+            const bool act = nan_normal && w > 0.f && c0 < nk_lane;
+            n_upd_w += (unsigned int)__popcll(__ballot(act));
+            if (!act) continue;
+            if (!gsdf_key_in_range(vx, vy, vz)) { atomicOr(&a.st->status, GSDF_STATUS_KEY_RANGE); continue; }
+            gsdf_payload* p = gsdf_find_or_insert(a.tab, gsdf_key_pack(vx, vy, vz));
+            if (!p) { atomicOr(&a.st->status, GSDF_STATUS_TABLE_FULL); continue; }
+            unsigned long long q0, qwz, qgxy;
+            fuse_pack((uint32_t)(w * FUSE_FIX_W), f2fix(w * __builtin_amdgcn_fmed3f(sdf, -g.T, g.T)), 0, 0, 0, q0, qwz, qgxy);
+            const fuse_sums d = fuse_unpack(q0, qwz, qgxy);
+            defer_append(a, p, d.w, d.s, w * Rn.x * FUSE_FIX_G_INV, w * Rn.y * FUSE_FIX_G_INV, w * Rn.z * FUSE_FIX_G_INV);
+            L.any_defer = 1u;
+            vis_mark(a, p, frame_cur);
         }
     }
     if (GSDF_EXPERIMENT(a.debug, 128) && lane == 0) {

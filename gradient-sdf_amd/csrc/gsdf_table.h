@@ -7,7 +7,8 @@
  * with a hash map of 4x4x4 VOXEL BLOCKS (the surface band is ~21 voxels thick, so blocks that exist
  * are ~70 % full):
  *
- *   bkeys[n_blocks]      u64 block key: (x>>2, y>>2, z>>2) + 2^18, 19 bits each (x low); ~0 = empty.
+ *   bkeys[n_blocks]      u64 block key: ((x, y, z) + 2^20) >> 2 of a voxel index in [-2^20, 2^20) (GSDF_KEY_OFF), 19 bits
+ *                        each (x low); ~0 = empty.
  *                        Open addressing, double hashing; entry i owns block i.  65536 blocks (the
  *                        2^22-voxel default) = 512 KB of keys: the probe runs out of the L2.
  *                        Capacity: 2^c voxel records = 2^(c-6) blocks; a surface map fills its blocks to

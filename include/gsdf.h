@@ -114,7 +114,11 @@ int gsdf_get_map_type(gsdf_ctx* c, int* type);
 int gsdf_set_zrange(gsdf_ctx* c, float zmin, float zmax);
 
 /* new cv::NormalEstimator<float>(W, H, K, Size(win,win)) -> cache() -- normals/NormalEstimator.h:81-165,
- * main_scan_3d.cpp:183.  Also fixes the frame size all later calls must use. */
+ * main_scan_3d.cpp:183.  Also fixes the frame size all later calls must use.
+ * win: the side of the box window, odd, 1 .. 15 (the reference's scanner passes 11); a frame may be smaller than the window
+ * (BORDER_REFLECT_101 folds it over as often as needed).  win = 1 is accepted and is what the reference computes: the moment
+ * matrix of one pixel is singular and most normals are not finite.  An even, non-positive or larger win (or W, H <= 0, K null)
+ * is GSDF_ERR_INVALID; the arguments are checked before anything is released, so the context keeps the frame set-up it had. */
 int gsdf_normals_init(gsdf_ctx* c, int W, int H, const float K[9], int win);
 /* the 11 cached planes (x0,y0,x0/n2,y0/n2,1/n2,Q11,Q12,Q13,Q22,Q23,Q33) copied to the host */
 int gsdf_normals_cache(gsdf_ctx* c, float* planes11_host);
@@ -123,7 +127,21 @@ int gsdf_normals_compute(gsdf_ctx* c, const float* depth_host, float* nx, float*
 
 /* Sdf::update(color, depth, K, pose, NEst) -- Sdf.h:117, MapGradPixelSdf.cpp:43-122.
  * color is ignored by the reference and is not part of this ABI.  Synchronous; returns
- * GSDF_ERR_TABLE_FULL / GSDF_ERR_KEY_RANGE if the launch reported one. */
+ * GSDF_ERR_TABLE_FULL / GSDF_ERR_KEY_RANGE if the launch reported one.
+ * GSDF_ERR_KEY_RANGE: voxel indices are packed into 21 biased bits per axis, -2^20 <= index < 2^20 (+-20971.52 m at 2 cm voxels).
+ * A frame with samples beyond that is fused as if those samples' voxels did not exist: every packable voxel receives exactly
+ * what it would have received, the others are dropped, the frame is counted (gsdf_stats::frames, its vis_ bit), and n_valid /
+ * n_upd count every valid pixel and every sample with a positive weight, the dropped ones included.  The status is sticky: it
+ * is returned by this call, by gsdf_sync and by gsdf_track / gsdf_track_sampled until gsdf_reset, which clears it with the
+ * map; exports, queries and gsdf_get_stats keep working meanwhile.  gsdf_merge_raw[_dev] treat rows beyond the range the same
+ * way (refused, the other rows of the call merged); the readers (gsdf_query, gsdf_get_voxels, the raycaster, the mesh, the
+ * tracker) take a voxel beyond the range as missing, without an error.
+ * Depth values: a pixel is fused iff zmin < z < zmax holds as the reference writes it (`z <= zmin || z >= zmax` skips it), so
+ * 0, negative, +-inf and denormal depths are skipped -- but all of them enter the normals of the pixels around them as the
+ * reference's `z != 0 ? 1 / z : 0` gives them (a denormal: inf, i.e. no finite normal in its window).  A valid pixel whose
+ * normal is not finite passes the reference's gates (`<` comparisons) and is fused: distance and weight as usual, the gradient
+ * sum of its voxels NaN -- here as there (also most of a frame at win = 1).  A NaN depth passes the range gate in the reference
+ * and reaches a float -> int conversion of NaN (undefined behaviour): depth images must not hold NaN. */
 int gsdf_update(gsdf_ctx* c, const float* depth_host, const float R[9], const float t[3]);
 /* same with depth already resident in HBM; enqueue only.
  * Runs of this call are pipelined: the fusion of a frame is launched when the NEXT frame arrives (that launch's last workgroups
