@@ -165,6 +165,7 @@ def load(path=None):
         "gsdf_profile_read_launches": (C.c_int, [vp, C.c_int, fp, C.c_int64, i64p]),
         "gsdf_raycast": (C.c_int, [vp, fp, fp, fp, C.c_int, C.c_int, C.c_float, C.c_float, fp, fp]),
         "gsdf_extract_mesh": (C.c_int, [vp, C.c_float, C.POINTER(C.c_int8), fp, C.c_int64, C.POINTER(C.c_int64)]),
+        "gsdf_extract_mesh_indexed": (C.c_int, [vp, C.c_float, C.POINTER(C.c_int8), fp, fp, i32p, C.c_int64, C.c_int64, i64p, i64p]),
         "gsdf_dev_alloc": (C.c_int, [vp, C.POINTER(vp), C.c_int64]),
         "gsdf_dev_free": (C.c_int, [vp, vp]),
         "gsdf_dev_upload": (C.c_int, [vp, vp, vp, C.c_int64]),
@@ -205,6 +206,7 @@ ABI_SYMBOLS = [
     "gsdf_merge_allreduce", "gsdf_merge_allreduce_with", "gsdf_rccl_unique_id", "gsdf_rccl_comm_init", "gsdf_rccl_comm_count",
     "gsdf_rccl_comm_destroy",
     "gsdf_query", "gsdf_get_voxels", "gsdf_raycast", "gsdf_raycast_dev", "gsdf_raycast_counters", "gsdf_extract_mesh",
+    "gsdf_extract_mesh_indexed",
     "gsdf_dev_alloc", "gsdf_dev_free", "gsdf_dev_upload", "gsdf_dev_download", "gsdf_timer_start", "gsdf_timer_stop_ms",
     "gsdf_host_alloc", "gsdf_host_free", "gsdf_dev_upload_async", "gsdf_mark", "gsdf_mark_wait", "gsdf_mark_reached",
     "gsdf_dev_upload_ahead", "gsdf_upload_wait",
@@ -700,6 +702,22 @@ class GradSdf:
             self._chk(self.L.gsdf_extract_mesh(self.h, C.c_float(iso), tp, _fp(out), n.value, C.byref(n)))
         return out[:n.value]
 
+    def extract_mesh_indexed(self, tri_table=None, iso=0.0):
+        """gsdf_extract_mesh_indexed: (V float32 [nv, 3], N float32 [nv, 3], F int32 [nf, 3]) -- the triangles of extract_mesh
+        with one vertex per crossed grid edge, F in extract_mesh's order, N from the stored gradients (include/gsdf.h)."""
+        tp = None
+        if tri_table is not None:
+            tt = np.ascontiguousarray(tri_table, dtype=np.int8).reshape(256 * 16)
+            tp = tt.ctypes.data_as(C.POINTER(C.c_int8))
+        nv, nf = C.c_int64(0), C.c_int64(0)
+        self._chk(self.L.gsdf_extract_mesh_indexed(self.h, C.c_float(iso), tp, None, None, None, 0, 0, C.byref(nv), C.byref(nf)))
+        V = np.empty((max(nv.value, 1), 3), np.float32)
+        N = np.empty((max(nv.value, 1), 3), np.float32)
+        F = np.empty((max(nf.value, 1), 3), np.int32)
+        if nf.value:
+            self._chk(self.L.gsdf_extract_mesh_indexed(self.h, C.c_float(iso), tp, _fp(V), _fp(N), F.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                       nv.value, nf.value, C.byref(nv), C.byref(nf)))
+        return V[:nv.value], N[:nv.value], F[:nf.value]
 
     # -- timing -------------------------------------------------------------------------------
     def timer_start(self):

@@ -1607,6 +1607,99 @@ int gsdf_extract_mesh(gsdf_ctx* c, float iso, const int8_t tri_table[256 * 16], 
     return GSDF_OK;
 }
 
+/* The steps are listed at the head of gsdf_mesh_index.hip.  The counting pass is gsdf_extract_mesh's own sizing pass (k_mesh_bbox
+ * + k_mesh with no room): it leaves the bounding-box minimum on the device and the triangle count, so the corner pass runs once,
+ * into buffers of the exact size, whatever the caller's maxima are -- the vertex count is known only after the weld, and it is
+ * reported also when the caller's buffers are too small. */
+int gsdf_extract_mesh_indexed(gsdf_ctx* c, float iso, const int8_t tri_table[256 * 16], float* vertices_out, float* normals_out,
+                              int32_t* faces_out, int64_t max_vertices, int64_t max_faces, int64_t* n_vertices, int64_t* n_faces) {
+    GSDF_FLUSH(c);
+    if (!c || !n_vertices || !n_faces || (max_vertices > 0 && !vertices_out) || (max_faces > 0 && !faces_out))
+        return fail(GSDF_ERR_INVALID, "null argument");
+    if (!tri_table) tri_table = GSDF_MC_TRI_TABLE;
+    HIP_TRY(hipSetDevice(c->device));
+    *n_vertices = 0; *n_faces = 0;
+    gsdf_dev<int> d_mn;
+    gsdf_dev<signed char> d_tab;
+    HIP_TRY(d_mn.alloc(3));
+    HIP_TRY(d_tab.alloc(256 * 16));
+    const int big[3] = { 2147483647, 2147483647, 2147483647 };
+    HIP_TRY(hipMemcpyAsync(d_mn, big, sizeof(big), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_tab, tri_table, 256 * 16, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream));
+    unsigned long long n = 0, n2 = 0;
+    gsdf_launch_mesh(c->stream, c->tab, c->n_slots, c->voxel_size, iso, d_mn, d_tab, nullptr, nullptr, c->counter, 0);
+    HIP_TRY(hipMemcpyAsync(&n, c->counter, sizeof(n), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (n == 0) return GSDF_OK;
+    if (n > 2147483647ull / 3)
+        return fail(GSDF_ERR_INVALID, "gsdf_extract_mesh_indexed: more than (2^31 - 1) / 3 triangles (vertex ids and corner ranks are 32-bit)");
+    const size_t nt = (size_t)n, nc = 3 * nt;
+    gsdf_dev<float> d_tris;
+    gsdf_dev<unsigned long long> d_keys, d_keys2, d_ekeys, d_ck, d_ck2;
+    gsdf_dev<uint32_t> d_muw, d_idx, d_order, d_rank, d_rank2, d_heads, d_before;
+    gsdf_dev<void> d_tmp;
+    HIP_TRY(d_tris.alloc(nt * 9));
+    HIP_TRY(d_keys.alloc(nt));
+    HIP_TRY(d_keys2.alloc(nt));
+    HIP_TRY(d_ekeys.alloc(nc));
+    HIP_TRY(d_muw.alloc(nc));
+    HIP_TRY(d_idx.alloc(nt));
+    HIP_TRY(d_order.alloc(nt));
+    HIP_TRY(d_ck.alloc(nc));
+    HIP_TRY(d_ck2.alloc(nc));
+    HIP_TRY(d_rank.alloc(nc));
+    HIP_TRY(d_rank2.alloc(nc));
+    HIP_TRY(d_heads.alloc(nc));
+    HIP_TRY(d_before.alloc(nc));
+    size_t b0 = 0, b1 = 0, b2 = 0;
+    HIP_TRY(gsdf_sort_pairs_u64(nullptr, &b0, d_keys, d_keys2, d_idx, d_order, nt, c->stream));
+    HIP_TRY(gsdf_sort_pairs_u64(nullptr, &b1, d_ck, d_ck2, d_rank, d_rank2, nc, c->stream));
+    HIP_TRY(gsdf_run_heads_scan(nullptr, &b2, d_ck2, d_heads, d_before, nc, c->stream));
+    HIP_TRY(d_tmp.alloc(std::max<size_t>(std::max(b0, b1), std::max<size_t>(b2, 8))));
+    HIP_TRY(hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream));
+    gsdf_launch_mesh_corners(c->stream, c->tab, c->n_slots, c->voxel_size, iso, d_mn, d_tab, d_tris, d_keys, d_ekeys, d_muw, c->counter,
+                             (long long)nt);
+    HIP_TRY(hipMemcpyAsync(&n2, c->counter, sizeof(n2), hipMemcpyDeviceToHost, c->stream));
+    /* the soup's order, then the weld: stable sort of (edge key, corner rank), run starts, their scan */
+    gsdf_launch_iota(c->stream, d_idx, nt);
+    b0 = d_tmp.bytes();
+    HIP_TRY(gsdf_sort_pairs_u64(d_tmp, &b0, d_keys, d_keys2, d_idx, d_order, nt, c->stream));
+    gsdf_launch_corner_keys(c->stream, d_ekeys, d_order, d_ck, d_rank, nt);
+    b1 = d_tmp.bytes();
+    HIP_TRY(gsdf_sort_pairs_u64(d_tmp, &b1, d_ck, d_ck2, d_rank, d_rank2, nc, c->stream));
+    b2 = d_tmp.bytes();
+    HIP_TRY(gsdf_run_heads_scan(d_tmp, &b2, d_ck2, d_heads, d_before, nc, c->stream));
+    uint32_t last[2] = { 0u, 0u };
+    HIP_TRY(hipMemcpyAsync(&last[0], d_before + (nc - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&last[1], d_heads + (nc - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (n2 != n) return fail(GSDF_ERR_HIP, "gsdf_extract_mesh_indexed: the map changed between the counting and the corner pass");
+    const size_t nv = (size_t)last[0] + last[1];
+    *n_vertices = (int64_t)nv; *n_faces = (int64_t)nt;
+    if (max_vertices == 0 && max_faces == 0) return GSDF_OK;                    /* the sizing call */
+    if ((int64_t)nv > max_vertices || (int64_t)nt > max_faces)
+        return fail(GSDF_ERR_INVALID, "gsdf_extract_mesh_indexed: max_vertices or max_faces too small (n_vertices / n_faces hold the need)");
+    gsdf_dev<int32_t> d_faces;
+    gsdf_dev<float> d_v, d_n;
+    gsdf_dev<unsigned long long> d_vkeys;
+    gsdf_dev<uint32_t> d_vmuw;
+    HIP_TRY(d_faces.alloc(nc));
+    HIP_TRY(d_v.alloc(nv * 3));
+    HIP_TRY(d_vkeys.alloc(nv));
+    HIP_TRY(d_vmuw.alloc(nv));
+    if (normals_out) HIP_TRY(d_n.alloc(nv * 3));
+    gsdf_launch_weld(c->stream, d_ck2, d_rank2, d_heads, d_before, d_order, d_tris, d_muw, nc, d_faces, d_v, d_vkeys, d_vmuw);
+    if (normals_out) gsdf_launch_vertex_normals(c->stream, c->tab, d_mn, d_vkeys, d_vmuw, nv, d_n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(vertices_out, d_v, nv * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(faces_out, d_faces, nc * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (normals_out) HIP_TRY(hipMemcpyAsync(normals_out, d_n, nv * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return GSDF_OK;
+}
+
 int gsdf_block_keys_dev(gsdf_ctx* c, uint64_t* keys_dev, int64_t max_n, int64_t* n) {
     GSDF_FLUSH(c);
     if (!c || !n || (max_n > 0 && !keys_dev)) return fail(GSDF_ERR_INVALID, "null argument");

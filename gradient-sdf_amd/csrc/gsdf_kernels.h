@@ -201,6 +201,23 @@ hipError_t gsdf_sort_pairs_u64(void* tmp, size_t* tmp_bytes, const unsigned long
 void gsdf_launch_iota(hipStream_t s, uint32_t* idx, size_t n);
 void gsdf_launch_gather_tris(hipStream_t s, const float* tris, const uint32_t* order, float* sorted, size_t n);
 
+/* the indexed mesh (gsdf_mesh_index.hip): k_mesh's triangles with, per corner, the key of its grid edge (lower endpoint relative
+ * to mn_dev, z-y-x at 20 bits each, then the axis in 2 bits) and a word of interpolate's mu | walked-downwards << 31; the edge
+ * keys of the corners brought into sweep order with their ranks; run starts of the sorted keys and their exclusive scan (rocPRIM;
+ * tmp == nullptr: only *tmp_bytes is set); faces / vertex positions / per-vertex key and mu word; the normals */
+void gsdf_launch_mesh_corners(hipStream_t s, gsdf_table tab, size_t n_slots, float vs, float iso, const int* mn_dev,
+                              const signed char* tri_table_dev, float* tris_dev, unsigned long long* keys_dev,
+                              unsigned long long* ekeys_dev, uint32_t* muw_dev, unsigned long long* counter, long long max_tris);
+void gsdf_launch_corner_keys(hipStream_t s, const unsigned long long* ekeys, const uint32_t* order, unsigned long long* out,
+                             uint32_t* rank, size_t n_tris);
+hipError_t gsdf_run_heads_scan(void* tmp, size_t* tmp_bytes, const unsigned long long* sorted, uint32_t* heads, uint32_t* before, size_t n,
+                               hipStream_t s);
+void gsdf_launch_weld(hipStream_t s, const unsigned long long* sorted, const uint32_t* rank, const uint32_t* heads, const uint32_t* before,
+                      const uint32_t* order, const float* tris, const uint32_t* muw, size_t n_corners, int32_t* faces, float* vertices,
+                      unsigned long long* vkeys, uint32_t* vmuw);
+void gsdf_launch_vertex_normals(hipStream_t s, gsdf_table tab, const int* mn_dev, const unsigned long long* vkeys, const uint32_t* vmuw,
+                                size_t n_vertices, float* normals);
+
 /* dense block exchange (frame-sharded fusion): list of block keys; pack / unpack of 64 x 5 raw sums per listed block */
 void gsdf_launch_block_keys(hipStream_t s, gsdf_table tab, size_t n_blocks, unsigned long long* out_dev, unsigned long long* counter,
                             long long max_n);

@@ -2646,6 +2646,8 @@ __global__ __launch_bounds__(256) void k_mesh_bbox(gsdf_table tab, size_t n_slot
     }
 }
 
+/* k_mesh_corners (gsdf_mesh_index.hip) restates this kernel for the indexed mesh, whose faces must be these triangles: change the
+ * two together.  (One templated body for both was tried; it changed this kernel's generated code, which is to stay as it is.) */
 __global__ __launch_bounds__(256) void k_mesh(gsdf_table tab, size_t n_slots, float vs, float iso, const int* __restrict__ mn,
                                                const signed char* __restrict__ tri_table, float* __restrict__ tris,
                                                unsigned long long* __restrict__ keys, unsigned long long* counter, long long max_tris) {

@@ -137,3 +137,4 @@ SdfVoxel MapGradPixelSdf::getSdf(Vec3i idx) const {
 bool MapGradPixelSdf::extract_pc(std::string filename) { return gsdf_exports::write_cloud_ply(ctx_, voxel_size_, filename, nullptr); }
 bool MapGradPixelSdf::save_sdf(std::string filename) { return gsdf_exports::write_sdf_txt(ctx_, voxel_size_, filename); }
 bool MapGradPixelSdf::extract_mesh(std::string filename) { return gsdf_exports::write_mesh_ply(ctx_, voxel_size_, filename, nullptr); }
+bool MapGradPixelSdf::extract_mesh_indexed(std::string filename) { return gsdf_exports::write_indexed_mesh_ply(ctx_, filename, nullptr, nullptr); }

@@ -56,6 +56,9 @@ public:
     bool extract_pc(std::string filename) override;                    /* MapGradPixelSdf.cpp:177-220 */
     bool save_sdf(std::string filename) override;                      /* MapGradPixelSdf.cpp:222-296 */
     bool extract_mesh(std::string filename) override;                  /* MapGradPixelSdf.cpp:124-175 */
+    /* the same surface as an indexed mesh with a gradient normal per vertex, binary PLY (gsdf_extract_mesh_indexed; not in the
+     * reference).  MapPixelSdf inherits it: a base context stores the same gradient sums */
+    bool extract_mesh_indexed(std::string filename);
 
     /* fix the frame size / intrinsics / normal-estimator window before driving the *_dev entries directly (update() does
      * it on the first frame) */

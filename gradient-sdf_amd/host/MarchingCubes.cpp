@@ -5,6 +5,7 @@
 #include <charconv>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <fstream>
 #include <limits>
 #include <string>
@@ -183,5 +184,32 @@ bool MarchingCubes::savePly(const std::string& filename) const {
     bool ok = true;
     for (size_t c = 0; c < n_chunks; ++c) ok = ok && std::fwrite(vtxt[c].data(), 1, vtxt[c].size(), f) == vtxt[c].size();
     for (size_t c = 0; c < n_chunks; ++c) ok = ok && std::fwrite(ftxt[c].data(), 1, ftxt[c].size(), f) == ftxt[c].size();
+    return std::fclose(f) == 0 && ok;
+}
+
+#if defined(__BYTE_ORDER__) && __BYTE_ORDER__ != __ORDER_LITTLE_ENDIAN__
+#error "saveIndexedPly writes the host's floats and ints as they lie in memory: a little-endian host is assumed"
+#endif
+bool MarchingCubes::saveIndexedPly(const std::string& filename, const std::vector<float>& vertices, const std::vector<float>& normals,
+                                   const std::vector<int32_t>& faces) {
+    if (vertices.size() % 3 || faces.size() % 3 || normals.size() != vertices.size()) return false;
+    const size_t nv = vertices.size() / 3, nf = faces.size() / 3;
+    for (int32_t id : faces) if (id < 0 || (size_t)id >= nv) return false;
+    FILE* f = std::fopen(filename.c_str(), "wb");
+    if (!f) return false;
+    const bool head = std::fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n"
+                    "property float nx\nproperty float ny\nproperty float nz\nelement face %zu\n"
+                    "property list uchar int vertex_indices\nend_header\n", nv, nf) > 0;
+    std::vector<char> buf(nv * 24 + nf * 13);
+    char* p = buf.data();
+    for (size_t i = 0; i < nv; ++i) {
+        std::memcpy(p, &vertices[3 * i], 12); std::memcpy(p + 12, &normals[3 * i], 12);
+        p += 24;
+    }
+    for (size_t i = 0; i < nf; ++i) {
+        *p = 3; std::memcpy(p + 1, &faces[3 * i], 12);
+        p += 13;
+    }
+    const bool ok = head && std::fwrite(buf.data(), 1, buf.size(), f) == buf.size();
     return std::fclose(f) == 0 && ok;
 }

@@ -30,6 +30,11 @@ public:
     /* the classic triTable in the layout gsdf_extract_mesh takes: 256 x 16 edge ids, -1 terminated */
     static void fill_table(int8_t out[256 * 16]);
     bool savePly(const std::string& filename) const;
+    /* an indexed mesh (gsdf_extract_mesh_indexed: 3 floats per vertex and per normal, 3 ids per face) as binary_little_endian
+     * PLY: vertices x y z nx ny nz as float, faces as a uchar count (3) and int ids.  false: sizes that do not fit together, an
+     * id outside the vertices, or the file cannot be written */
+    static bool saveIndexedPly(const std::string& filename, const std::vector<float>& vertices, const std::vector<float>& normals,
+                               const std::vector<int32_t>& faces);
     const std::vector<Vec3f>& vertices() const { return vertices_; }
     const std::vector<std::array<int, 3>>& faces() const { return faces_; }
     /* the case tables (exposed for tests) */

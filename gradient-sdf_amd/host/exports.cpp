@@ -125,4 +125,16 @@ bool write_mesh_ply(gsdf_ctx* ctx, float voxel_size, const std::string& filename
     return mc.savePly(filename);
 }
 
+/* the sizing call, then the exact-size call */
+bool write_indexed_mesh_ply(gsdf_ctx* ctx, const std::string& filename, long* n_vertices, long* n_faces) {
+    int64_t nv = 0, nf = 0;
+    if (gsdf_extract_mesh_indexed(ctx, 0.f, nullptr, nullptr, nullptr, nullptr, 0, 0, &nv, &nf) != GSDF_OK || nf <= 0) return false;
+    std::vector<float> v((size_t)nv * 3), n((size_t)nv * 3);
+    std::vector<int32_t> f((size_t)nf * 3);
+    if (gsdf_extract_mesh_indexed(ctx, 0.f, nullptr, v.data(), n.data(), f.data(), nv, nf, &nv, &nf) != GSDF_OK) return false;
+    if (n_vertices) *n_vertices = (long)nv;
+    if (n_faces) *n_faces = (long)nf;
+    return MarchingCubes::saveIndexedPly(filename, v, n, f);
+}
+
 } // namespace gsdf_exports

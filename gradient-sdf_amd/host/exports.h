@@ -18,6 +18,9 @@ bool write_points_ply(gsdf_ctx* ctx, float voxel_size, const std::string& filena
 bool write_sdf_txt(gsdf_ctx* ctx, float voxel_size, const std::string& filename, bool normals = true);
 /* extract_mesh -- MapGradPixelSdf.cpp:124-175, marching cubes on the device; *n_faces (nullable) = faces written */
 bool write_mesh_ply(gsdf_ctx* ctx, float voxel_size, const std::string& filename, long* n_faces);
+/* the same surface as an indexed mesh with gradient normals (gsdf_extract_mesh_indexed; not in the reference), binary PLY
+ * (MarchingCubes::saveIndexedPly); *n_vertices / *n_faces (nullable) = what was written.  false for an empty mesh, like write_mesh_ply */
+bool write_indexed_mesh_ply(gsdf_ctx* ctx, const std::string& filename, long* n_vertices, long* n_faces);
 }
 
 #endif

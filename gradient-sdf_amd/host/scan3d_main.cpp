@@ -17,6 +17,8 @@
  *                     the per-voxel sums over the union of blocks), then rank 0 writes the outputs.  Tracked mode does
  *                     not shard (frame i needs the map of all frames < i);
  *   --transport shm   the exchange through host shared memory instead of RCCL: N ranks on ONE device (test boxes).
+ *   --mesh-indexed    additionally write <results>mesh_indexed.ply: the same surface with one vertex per crossed grid edge,
+ *                     faces as indices and gradient normals, binary PLY (gsdf_extract_mesh_indexed);
  * --scan-type grad-sdf (MapGradPixelSdf) or base-sdf (MapPixelSdf, the plain-SDF baseline, :99-114 / :226-233); base-sdf runs
  * on one GPU only (--gpus N > 1 refuses it).
  */
@@ -48,7 +50,7 @@ struct Options {
     std::string input, output = "../results/", pose_file = "pose.txt", stype = "map-gp", dtype;
     size_t first = 0, last = std::numeric_limits<size_t>::max();
     float voxel_size = 0.01f, trunc = 5.f;
-    bool save_sdf = false, sync = false;
+    bool save_sdf = false, sync = false, mesh_indexed = false;
     int width = 640, height = 480, capacity_log2 = 22, device = 0;
     int max_capacity_log2 = 28;          /* the table doubles by itself up to this (the reference's map has no capacity) */
     int gpus = 1, rank = -1, decode_threads = 0;
@@ -62,10 +64,11 @@ bool parse(int argc, char** argv, Options& o) {
         std::string v;
         if (a == "--save-sdf") { o.save_sdf = true; continue; }
         if (a == "--sync") { o.sync = true; continue; }
+        if (a == "--mesh-indexed") { o.mesh_indexed = true; continue; }
         if (a == "-h" || a == "--help") {
             std::cout << "Hash Table-Based 3D Scanning (MI355X)\n  --input --results --pose-file --first --last --scan-type"
                          " --data-type --voxel-size --trunc --save-sdf --width --height --hash-capacity --hash-max-capacity --device"
-                         " --sync --decode-threads --gpus --transport rccl|shm\n"
+                         " --sync --decode-threads --gpus --transport rccl|shm --mesh-indexed\n"
                          "  --scan-type grad-sdf|base-sdf (base-sdf: one GPU only, --gpus 1)\n";
             std::exit(0);
         }
@@ -440,6 +443,12 @@ int run(int, char**, Options& opt) {
     std::string filename = opt.output + prefix + "_mesh_final.ply";
     if (!tSDF->extract_mesh(filename)) std::cerr << "Could not save mesh to " << filename << "!" << std::endl;
     T.toc("Save mesh to disk");
+    if (opt.mesh_indexed) {
+        T.tic();
+        filename = opt.output + "mesh_indexed.ply";
+        if (!tSDF->extract_mesh_indexed(filename)) std::cerr << "Could not save indexed mesh to " << filename << "!" << std::endl;
+        T.toc("Save indexed mesh to disk");
+    }
     T.tic();
     filename = opt.output + prefix + "_cloud_final.ply";
     if (!tSDF->extract_pc(filename)) std::cerr << "Could not save point cloud to " << filename << "!" << std::endl;

@@ -434,6 +434,39 @@ int gsdf_raycast_counters(gsdf_ctx* c, int64_t* samples, int64_t* records, int r
 int gsdf_extract_mesh(gsdf_ctx* c, float iso, const int8_t tri_table[256 * 16], float* triangles_out, int64_t max_tris,
                       int64_t* n_tris);
 
+/* The same iso-surface as an INDEXED mesh: one vertex per crossed grid edge, faces as vertex ids, a normal per vertex from the
+ * stored gradients.  Not in the reference (its meshes are triangle soups, computeTriangles :686-712 pushes three fresh vertices
+ * per face); defined on top of gsdf_extract_mesh (computeIsoSurface / computeLutIndex / interpolate,
+ * mesh/LayeredMarchingCubesNoColor.cpp:354-712) and of the cloud export's normal (extract_pc, MapGradPixelSdf.cpp:186-192:
+ * normal = -g^).
+ *  - Faces: exactly the triangles of gsdf_extract_mesh(iso, tri_table), in its order (z-y-x sweep, table order within a cube)
+ *    and with its corner order.  The degenerate-triangle rule is the soup's (:686-712: position equality of the cube's own three
+ *    interpolations); nothing is filtered again after welding.  The three ids of a face are distinct (a table triangle names
+ *    three different cube edges).
+ *  - Vertex identity: the GRID EDGE a corner lies on -- its lower endpoint voxel relative to the bounding-box minimum (z, then
+ *    y, then x, 20 bits each, as the sweep order's key) followed by the axis (0 x, 1 y, 2 z) in 2 bits.  Position bits are not
+ *    the identity: neighbouring cubes walk a grid edge in opposite directions (cube edge 0 runs -y, edge 2 +y: getVertex
+ *    :410-549) and interpolate (:642-662) need not give the same bits from both ends.  Vertex ids are the ranks of the distinct
+ *    edge keys in ascending order.
+ *  - Position: that of the vertex's CANONICAL corner, the first soup corner on the edge in sweep order (face index, then corner
+ *    0..2): interpolate's result for that cube, unchanged.  So vertices[faces[f][k]] differs from the soup's corner only where the
+ *    other direction of the walk rounds differently.
+ *  - Normal (normals_out, nullable): from the same canonical corner, with its endpoints a -> b as its cube walks the edge and
+ *    interpolate's mu (0, 1, 0 on the three 1e-7 guard returns :645-650, else the clamped quotient):
+ *    n = -normalized((1 - mu) g^_a + mu g^_b) in float, g^ the normalised stored gradient sum of the endpoint voxel as gsdf_query
+ *    and the cloud export normalise it; (0, 0, 0) when the blend's norm is 0 or not finite.  Base contexts store the same sums.
+ * Conventions of gsdf_extract_mesh: tri_table NULL = the reference's table; max_vertices = max_faces = 0 sizes the buffers;
+ * *n_vertices and *n_faces are always reported; if either maximum is too small nothing is written to any buffer and the call
+ * returns GSDF_ERR_INVALID; an empty map gives 0 / 0 and GSDF_OK; the table is only read; coordinates relative to the
+ * bounding-box minimum are taken at 20 bits per axis, as in gsdf_extract_mesh's sweep key -- an edge's lower endpoint may lie one
+ * voxel beyond a cube's anchor, so the keys are distinct for a bounding box of up to 2^20 - 1 voxels per axis (the sweep key's
+ * limit is 2^20).  At most (2^31 - 1) / 3 faces.
+ * Deterministic: the same map gives the same bytes, run to run and across gsdf_grow. */
+int gsdf_extract_mesh_indexed(gsdf_ctx* c, float iso, const int8_t tri_table[256 * 16],
+                              float* vertices_out /* 3 per vertex */, float* normals_out /* 3 per vertex, nullable */,
+                              int32_t* faces_out /* 3 per face */, int64_t max_vertices, int64_t max_faces,
+                              int64_t* n_vertices, int64_t* n_faces);
+
 /* device-memory plumbing so callers can stage frames in HBM without another runtime */
 int gsdf_dev_alloc(gsdf_ctx* c, void** dev_ptr, int64_t bytes);
 int gsdf_dev_free(gsdf_ctx* c, void* dev_ptr);          /* withdraws a next-frame hint that lies in the freed allocation */
