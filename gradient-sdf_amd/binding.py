@@ -81,6 +81,8 @@ def load_test_lib():
         f = getattr(L, name)
         f.restype = C.c_int
         f.argtypes = args
+    L.gsdf_debug_ba_delta.restype = C.c_int             # the 6n components of the last coupled pose step's solution
+    L.gsdf_debug_ba_delta.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.gsdf_debug_fail_alloc.restype = C.c_int           # process-wide: the nth owned allocation from now on fails once (0 disarms)
     L.gsdf_debug_fail_alloc.argtypes = [C.c_int]
     return L
@@ -133,6 +135,9 @@ def load(path=None):
         "gsdf_ba_solve_dist": (C.c_int, [vp, C.c_float]),
         "gsdf_ba_optimize": (C.c_int, [vp, C.c_int, fp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "gsdf_ba_get_poses": (C.c_int, [vp, fp]),
+        "gsdf_ba_pose_system": (C.c_int, [vp, fp, fp]),
+        "gsdf_ba_solve_pose_full": (C.c_int, [vp, C.c_float]),
+        "gsdf_ba_set_pose_step": (C.c_int, [vp, C.c_int]),
         "gsdf_ba_counters": (C.c_int, [vp, i64p, i64p]),
         "gsdf_color_compute": (C.c_int, [vp, C.c_int, fp, fp, C.POINTER(C.c_int), i64p]),
         "gsdf_color_export": (C.c_int, [vp, i32p, fp, C.c_int64, i64p]),
@@ -200,6 +205,7 @@ ABI_SYMBOLS = [
     "gsdf_track", "gsdf_track_sampled", "gsdf_hint_next_depth_dev", "gsdf_track_and_fuse_ahead_dev", "gsdf_set_pose", "gsdf_get_pose", "gsdf_track_and_fuse_dev", "gsdf_read_frame_log",
     "gsdf_sync", "gsdf_get_stats", "gsdf_count", "gsdf_export", "gsdf_enable_vis", "gsdf_export_vis",
     "gsdf_ba_setup", "gsdf_ba_set_loss", "gsdf_ba_energy", "gsdf_ba_solve_pose", "gsdf_ba_solve_dist", "gsdf_ba_optimize", "gsdf_ba_get_poses", "gsdf_ba_counters",
+    "gsdf_ba_pose_system", "gsdf_ba_solve_pose_full", "gsdf_ba_set_pose_step",
     "gsdf_color_compute", "gsdf_color_export", "gsdf_color_cloud", "gsdf_color_counters", "gsdf_color_mesh", "gsdf_grow", "gsdf_set_auto_grow", "gsdf_capacity", "gsdf_merge_from", "gsdf_create_shards", "gsdf_merge_prepare",
     "gsdf_merge_raw", "gsdf_export_raw_dev",
     "gsdf_merge_raw_dev", "gsdf_block_keys_dev", "gsdf_pack_blocks_dev", "gsdf_unpack_blocks_dev",
@@ -491,6 +497,27 @@ class GradSdf:
         ne, conv = C.c_int(0), C.c_int(0)
         self._chk(self.L.gsdf_ba_optimize(self.h, int(max_it), _fp(e), C.byref(ne), C.byref(conv)))
         return bool(conv.value), e[:ne.value]
+
+    def ba_pose_system(self):
+        """gsdf_ba_pose_system: (H, b) of the coupled pose step (solvePoseFull) at the current state, H (6n, 6n), b (6n,)"""
+        n = getattr(self, "_ba_n", 1)
+        H = np.zeros((6 * n, 6 * n), np.float32)
+        b = np.zeros(6 * n, np.float32)
+        self._chk(self.L.gsdf_ba_pose_system(self.h, _fp(H), _fp(b)))
+        return H, b
+
+    def ba_solve_pose_full(self, damping=1.0):
+        self._chk(self.L.gsdf_ba_solve_pose_full(self.h, np.float32(damping)))
+
+    def debug_ba_delta(self):
+        """the solution delta (6n,) of the last ba_solve_pose_full; test build only (lib=load_test_lib())"""
+        d = np.zeros(6 * self._ba_n, np.float32)
+        self._chk(self.L.gsdf_debug_ba_delta(self.h, _fp(d)))
+        return d
+
+    def ba_set_pose_step(self, mode):
+        """the pose step of ba_optimize: 0 = solvePose (decoupled, the default), 1 = solvePoseFull (coupled)"""
+        self._chk(self.L.gsdf_ba_set_pose_step(self.h, int(mode)))
 
     def merge_prepare(self, nranks):
         self._chk(self.L.gsdf_merge_prepare(self.h, int(nranks)))

@@ -1235,7 +1235,7 @@ int gsdf_ba_setup(gsdf_ctx* c, int n, const float* images_bgr_host, const float*
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->ba = gsdf_ba_bufs();                                   /* the old setup goes first; until the commit below there is none */
-    c->ba_n = 0; c->ba_gate_fresh = false; c->ba_mean_valid = false;
+    c->ba_n = 0; c->ba_gate_fresh = false; c->ba_mean_valid = false; c->ba_pose_step = 0;
     gsdf_ba_bufs b;
     const size_t img_count = (size_t)n * c->W * c->H * 3;
     HIP_TRY(b.images.alloc(img_count));
@@ -1343,6 +1343,21 @@ int gsdf_ba_solve_dist(gsdf_ctx* c, float damping) {
     return GSDF_OK;
 }
 
+/* one keyframe's update from its six components of the step: t_i -= dp[0..2], R_i = R_i * SO3::exp(-dp[3..5]) (solvePose
+ * :584-588, solvePoseFull :491-494) */
+static void ba_apply_delta(gsdf_ctx* c, int i, const float* dp) {
+    for (int k = 0; k < 3; ++k) c->ba_t[3 * i + k] -= dp[k];
+    float pose[7] = { 0, 0, 0, 0, 0, 0, 1 };
+    const float xi[6] = { 0, 0, 0, -dp[3], -dp[4], -dp[5] };
+    gsdf_se3_exp_mul(xi, pose);                               /* SO3::exp(-omega) */
+    float Ex[9], Rn[9];
+    gsdf_quat_to_R(pose + 3, Ex);
+    const float* Ri = &c->ba_R[9 * (size_t)i];
+    for (int r = 0; r < 3; ++r)
+        for (int k = 0; k < 3; ++k) Rn[3 * r + k] = gsdf_sum3(Ri[3 * r] * Ex[k], Ri[3 * r + 1] * Ex[3 + k], Ri[3 * r + 2] * Ex[6 + k]);
+    std::memcpy(&c->ba_R[9 * (size_t)i], Rn, sizeof(Rn));
+}
+
 /* the pose sweep + the per-keyframe 6x6 solves; wait_upload: block until the new poses are on the device (the public entry)
  * or leave the copy queued in front of whatever the caller enqueues next (gsdf_ba_optimize) */
 static int ba_solve_pose(gsdf_ctx* c, bool wait_upload) {
@@ -1364,16 +1379,7 @@ static int ba_solve_pose(gsdf_ctx* c, bool wait_upload) {
         bool nan = false;
         for (int k = 0; k < 6; ++k) nan = nan || std::isnan(dp[k]);
         if (nan) continue;
-        for (int k = 0; k < 3; ++k) c->ba_t[3 * i + k] -= dp[k];
-        float pose[7] = { 0, 0, 0, 0, 0, 0, 1 };
-        const float xi[6] = { 0, 0, 0, -dp[3], -dp[4], -dp[5] };
-        gsdf_se3_exp_mul(xi, pose);                           /* SO3::exp(-omega) */
-        float Ex[9], Rn[9];
-        gsdf_quat_to_R(pose + 3, Ex);
-        const float* Ri = &c->ba_R[9 * (size_t)i];
-        for (int r = 0; r < 3; ++r)
-            for (int k = 0; k < 3; ++k) Rn[3 * r + k] = gsdf_sum3(Ri[3 * r] * Ex[k], Ri[3 * r + 1] * Ex[3 + k], Ri[3 * r + 2] * Ex[6 + k]);
-        std::memcpy(&c->ba_R[9 * (size_t)i], Rn, sizeof(Rn));
+        ba_apply_delta(c, i, dp);
     }
     if (wait_upload) return ba_upload_poses(c);
     /* c->ba_R / ba_t are members: they stay untouched until the caller's next synchronisation, which is behind these copies */
@@ -1394,6 +1400,101 @@ int gsdf_ba_solve_pose(gsdf_ctx* c, float damping) {
     return ba_solve_pose(c, true);
 }
 
+/* ---- solvePoseFull (:392-496): the coupled 6n x 6n system ---- */
+/* H (6n)^2 row-major, b 6n, at the current state.  The diagonal blocks and b are the pose sweep's 27 sums per keyframe -- bit for
+ * bit what the decoupled step solves -- and the off-diagonal blocks come from the contraction of gsdf_ba_full.hip.  Its two
+ * buffers are allocated here, by the first coupled call after a gsdf_ba_setup. */
+static int ba_full_system(gsdf_ctx* c, std::vector<float>& H, std::vector<float>& b) {
+    const int n = c->ba_n, N = 6 * n;
+    HIP_TRY(c->ba.full_part.grow(gsdf_ba_full_part_floats(n)));
+    HIP_TRY(c->ba.full_H.grow((size_t)N * N));
+    const bool list_was_fresh = c->ba_gate_fresh;
+    ba_refresh_gate(c);
+    const gsdf_ba_dev d = ba_dev(c);
+    gsdf_launch_ba_pose(c->stream, d, c->ba.block_part, c->ba.Hb, c->ba_mean_valid && list_was_fresh);
+    gsdf_launch_ba_full(c->stream, d, c->ba.full_part, c->ba.full_H);
+    HIP_TRY(hipGetLastError());
+    std::vector<float> hb((size_t)n * 27);
+    H.resize((size_t)N * N); b.resize((size_t)N);
+    HIP_TRY(hipMemcpyAsync(hb.data(), c->ba.Hb, hb.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(H.data(), c->ba.full_H, H.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < n; ++i) {                             /* :461-466 */
+        const float* v = &hb[27 * (size_t)i];
+        for (int k = 0; k < 6; ++k) b[6 * (size_t)i + k] = v[k];
+        int q = 6;
+        for (int a1 = 0; a1 < 6; ++a1)
+            for (int a2 = a1; a2 < 6; ++a2) {
+                H[(size_t)(6 * i + a1) * N + 6 * i + a2] = v[q]; H[(size_t)(6 * i + a2) * N + 6 * i + a1] = v[q]; ++q;
+            }
+    }
+    return GSDF_OK;
+}
+int gsdf_ba_pose_system(gsdf_ctx* c, float* H, float* b) {
+    GSDF_FLUSH(c);
+    int rc = ba_require(c);
+    if (rc) return rc;
+    if (!H && !b) return fail(GSDF_ERR_INVALID, "null argument (H and b)");
+    if (c->ba_mean_on != 2) {
+        c->ba_gate_fresh = false;                             /* the map may have changed since the last BA call */
+        c->ba_mean_valid = false;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<float> Hh, bh;
+    if ((rc = ba_full_system(c, Hh, bh))) return rc;
+    if (H) std::memcpy(H, Hh.data(), Hh.size() * sizeof(float));
+    if (b) std::memcpy(b, bh.data(), bh.size() * sizeof(float));
+    return GSDF_OK;
+}
+/* the coupled system + one LDLT of the whole of it (:483) + the pose update; wait_upload as in ba_solve_pose */
+static int ba_solve_pose_full(gsdf_ctx* c, bool wait_upload) {
+    const int n = c->ba_n;
+    std::vector<float> H, b;
+    int rc = ba_full_system(c, H, b);
+    if (rc) return rc;
+    c->ba_mean_valid = false;                                 /* the poses move */
+    std::vector<float> delta((size_t)6 * n);
+    gsdf_ldlt_solve(6 * n, H.data(), b.data(), delta.data());
+    bool nan = false;                                         /* :488-490: any NaN and no pose moves */
+    for (float v : delta) nan = nan || std::isnan(v);
+    if (!nan)
+        for (int i = 0; i < n; ++i) ba_apply_delta(c, i, &delta[6 * (size_t)i]);
+#ifdef GSDF_EXPERIMENTS
+    c->ba_last_delta = delta;
+#endif
+    if (wait_upload) return ba_upload_poses(c);
+    HIP_TRY(hipMemcpyAsync(c->ba.Rt, c->ba_R.data(), c->ba_R.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->ba.Rt + 9 * (size_t)c->ba_n, c->ba_t.data(), c->ba_t.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    return GSDF_OK;
+}
+int gsdf_ba_solve_pose_full(gsdf_ctx* c, float damping) {
+    GSDF_FLUSH(c);
+    (void)damping;                                            /* unused by the reference as well (:392) */
+    int rc = ba_require(c);
+    if (rc) return rc;
+    if (c->ba_mean_on != 2) {
+        c->ba_gate_fresh = false;                             /* the map may have changed since the last BA call */
+        c->ba_mean_valid = false;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    return ba_solve_pose_full(c, true);
+}
+int gsdf_ba_set_pose_step(gsdf_ctx* c, int mode) {
+    int rc = ba_require(c);
+    if (rc) return rc;
+    if (mode != 0 && mode != 1) return fail(GSDF_ERR_INVALID, "pose step must be 0 (solvePose) or 1 (solvePoseFull)");
+    c->ba_pose_step = mode;
+    return GSDF_OK;
+}
+#ifdef GSDF_EXPERIMENTS
+/* test build only: the 6n components of the last coupled step's solution */
+int gsdf_debug_ba_delta(gsdf_ctx* c, float* delta) {
+    if (!c || !delta || c->ba_last_delta.size() != (size_t)6 * c->ba_n) return GSDF_ERR_INVALID;
+    std::memcpy(delta, c->ba_last_delta.data(), c->ba_last_delta.size() * sizeof(float));
+    return GSDF_OK;
+}
+#endif
+
 /* optimize (:611-662).  Per iteration the host needs two things from the device: the 27 sums per keyframe of the pose sweep
  * (it solves the 6x6 systems) and, for the stop rule, the two energies.  So an iteration synchronises twice: behind the pose
  * sweep, and ONCE behind [energy -> distance sweep -> energy], both energies in one read (they used to be four waits). */
@@ -1412,7 +1513,7 @@ int gsdf_ba_optimize(gsdf_ctx* c, int max_it, float* energies, int* n_energies, 
     const size_t set = (size_t)3 * gsdf_ba_blocks();
     std::vector<double> h(2 * set);
     for (int iter = 0; iter < max_it; ++iter) {               /* :621-657 */
-        if ((rc = ba_solve_pose(c, false))) return rc;
+        if ((rc = c->ba_pose_step ? ba_solve_pose_full(c, false) : ba_solve_pose(c, false))) return rc;   /* :627-628 */
         if ((rc = ba_energy_enqueue(c, 0, false))) return rc;  /* (the distance sweep follows: nobody reads its means) */
         if ((rc = ba_dist_enqueue(c, 1.0f))) return rc;
         if ((rc = ba_energy_enqueue(c, 1))) return rc;

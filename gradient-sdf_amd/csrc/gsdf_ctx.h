@@ -165,6 +165,8 @@ struct gsdf_ba_bufs {
     gsdf_dev<void> gate_tmp;                       /* rocPRIM select scratch */
     gsdf_dev<unsigned long long> counter2;         /* device word: entries of gate_list */
     gsdf_dev<void> mean;                           /* per entry of gate_list: what the last energy sweep's first loop found (24 B each; gsdf_ba_dev::mean_cache) */
+    gsdf_dev<float> full_part;                     /* the coupled pose system's per-workgroup partial tiles (allocated by the first coupled call) */
+    gsdf_dev<float> full_H;                        /* ... and its (6n)^2 matrix */
 };
 
 /* ColorUpsampler (gsdf_color.hip): the snapshot and the scratch of its compute; the buffers grow and are kept */
@@ -241,6 +243,10 @@ struct gsdf_ctx {
     gsdf_ba_bufs ba;
     std::vector<float> ba_R, ba_t;                 /* host copies of the keyframe poses being optimised */
     bool ba_gate_fresh = false;                    /* ba.gate_list matches the distances in the table */
+    int ba_pose_step = 0;                          /* gsdf_ba_set_pose_step: the pose step of gsdf_ba_optimize (0 solvePose, 1 solvePoseFull) */
+#ifdef GSDF_EXPERIMENTS
+    std::vector<float> ba_last_delta;              /* gsdf_debug_ba_delta */
+#endif
     int ba_mean_on = 1;                            /* GSDF_BA_MEAN_CACHE (read by gsdf_ba_setup) */
     bool ba_mean_valid = false;                    /* ... at the very state (poses, distances, gate list) the next pose sweep will see */
     long long ba_last_voxels = 0, ba_last_obs = 0; /* what the last energy sweep read back counted (gsdf_ba_counters) */

@@ -263,5 +263,9 @@ void gsdf_launch_ba_energy(hipStream_t s, const gsdf_ba_dev& d, double* block_E,
 void gsdf_launch_ba_dist(hipStream_t s, const gsdf_ba_dev& d, float damping, double* block_cnt /* nullable: [2][gsdf_ba_blocks()] voxels, observations */);
 void gsdf_launch_ba_pose(hipStream_t s, const gsdf_ba_dev& d, float* block_part, float* out, bool use_mean_cache = false /* written by an energy sweep at this very state */);
 int  gsdf_ba_blocks(void);
+/* the coupled pose system (gsdf_ba_full.hip): -S = the off-diagonal 6x6 blocks of the (6n)^2 row-major H, both triangles; the
+ * diagonal blocks of H are not written.  part: gsdf_ba_full_part_floats(n) floats of per-workgroup partial tiles */
+void gsdf_launch_ba_full(hipStream_t s, const gsdf_ba_dev& d, float* part, float* H);
+size_t gsdf_ba_full_part_floats(int n);
 
 #endif /* GSDF_KERNELS_H_ */

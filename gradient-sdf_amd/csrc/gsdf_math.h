@@ -13,6 +13,7 @@
 
 #include <math.h>
 #include <stdint.h>
+#include <vector>
 
 #if defined(__HIPCC__)
 #define GSDF_HD __host__ __device__ __forceinline__
@@ -303,6 +304,39 @@ GSDF_HD void gsdf_ldlt_solve6(const float* Hin, const float* bin, float* x) {
     for (int i = 0; i < 6; ++i) bb[i] = A[7 * i] != 0.f ? bb[i] / A[7 * i] : 0.f;
     for (int i = 5; i >= 0; --i) for (int j = i + 1; j < 6; ++j) bb[i] -= A[6 * j + i] * bb[j];
     for (int i = 0; i < 6; ++i) x[perm[i]] = bb[i];
+}
+
+/* gsdf_ldlt_solve6's algorithm for any N (the coupled pose step's 6n x 6n system, N <= 384; PhotometricOptimizer.cpp:483): the
+ * same pivot rule, the same operations in the same order -- at N = 6 the same bits -- and a zero pivot gives a zero component.
+ * Host only.  The column of L is copied out so that the update of the trailing rows runs over contiguous memory. */
+inline void gsdf_ldlt_solve(int N, const float* Hin, const float* bin, float* x) {
+    std::vector<float> A(Hin, Hin + (size_t)N * N), bb((size_t)N), col((size_t)N);
+    std::vector<int> perm((size_t)N);
+    for (int i = 0; i < N; ++i) perm[i] = i;
+    for (int k = 0; k < N; ++k) {
+        int piv = k;
+        float best = fabsf(A[(size_t)k * N + k]);
+        for (int i = k + 1; i < N; ++i) if (fabsf(A[(size_t)i * N + i]) > best) { best = fabsf(A[(size_t)i * N + i]); piv = i; }
+        if (piv != k) {
+            for (int j = 0; j < N; ++j) { const float tmp = A[(size_t)k * N + j]; A[(size_t)k * N + j] = A[(size_t)piv * N + j]; A[(size_t)piv * N + j] = tmp; }
+            for (int j = 0; j < N; ++j) { const float tmp = A[(size_t)j * N + k]; A[(size_t)j * N + k] = A[(size_t)j * N + piv]; A[(size_t)j * N + piv] = tmp; }
+            const int tp = perm[k]; perm[k] = perm[piv]; perm[piv] = tp;
+        }
+        const float d = A[(size_t)k * N + k];
+        if (d == 0.f) continue;
+        for (int i = k + 1; i < N; ++i) { A[(size_t)i * N + k] /= d; col[i] = A[(size_t)i * N + k]; }
+        for (int i = k + 1; i < N; ++i) {
+            float* Ai = &A[(size_t)i * N];
+            const float lid = Ai[k] * d;
+            for (int j = k + 1; j <= i; ++j) Ai[j] -= lid * col[j];
+            for (int j = k + 1; j < i; ++j) A[(size_t)j * N + i] = Ai[j];
+        }
+    }
+    for (int i = 0; i < N; ++i) bb[i] = bin[perm[i]];
+    for (int i = 0; i < N; ++i) for (int j = 0; j < i; ++j) bb[i] -= A[(size_t)i * N + j] * bb[j];
+    for (int i = 0; i < N; ++i) bb[i] = A[(size_t)i * N + i] != 0.f ? bb[i] / A[(size_t)i * N + i] : 0.f;
+    for (int i = N - 1; i >= 0; --i) for (int j = i + 1; j < N; ++j) bb[i] -= A[(size_t)j * N + i] * bb[j];
+    for (int i = 0; i < N; ++i) x[perm[i]] = bb[i];
 }
 
 #endif /* GSDF_MATH_H_ */

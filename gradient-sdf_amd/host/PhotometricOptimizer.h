@@ -3,6 +3,8 @@
  * (cpp/include/ps_optimizer/PhotometricOptimizer.h:68-186) as a facade over the C-ABI (gsdf_ba_*).
  * The voxel sweeps (getEnergy, solvePose's normal equations, solveDist) run on the GPU over the
  * HBM table; the per-keyframe 6x6 LDLT and the pose update are host-side glue inside libgsdf.
+ * solvePoseFull, the coupled 6n x 6n step (.h:180, .cpp:392-496), assembles its off-diagonal blocks on the GPU as well; optimize()
+ * runs it instead of solvePose when OptSettings::pose_step asks for it (the swap .cpp:627-628 invites).
  * The map must have been fused with visibility tracking (MapGradPixelSdf::enable_vis()).
  */
 #ifndef GSDF_HOST_PHOTOMETRIC_OPTIMIZER_H_
@@ -16,6 +18,8 @@
 #include "MapGradPixelSdf.h"
 
 enum LossFunction { L2 = 0, CAUCHY = 1, HUBER = 2, TUKEY = 3, TRUNC_L2 = 4 };   /* loss.h:39-46 */
+/* the pose step of optimize(): the reference's source chooses by commenting one line out (.cpp:627-628) */
+enum PoseStep { POSE_STEP_DECOUPLED = 0 /* solvePose */, POSE_STEP_FULL = 1 /* solvePoseFull */ };
 
 struct OptSettings {                       /* PhotometricOptimizer.h:49-66 */
     int max_it = 25;
@@ -24,6 +28,7 @@ struct OptSettings {                       /* PhotometricOptimizer.h:49-66 */
     float lambda = 0.5f;                   /* lambda of the weight function (not the LM damping) */
     float reg_weight = 10.0f;
     LossFunction loss = CAUCHY;            /* only TRUNC_L2 changes the computation, as in the reference (:364, :542) */
+    PoseStep pose_step = POSE_STEP_DECOUPLED;   /* not in the reference's struct: its optimize() calls solvePose (.cpp:628) */
 };
 
 /* float BGR image in [0,1], rows x cols x 3 (cv::Mat CV_32FC3 as produced by ImageLoader::load_color) */
@@ -74,11 +79,14 @@ public:
     float getEnergy() { upload(); float E = 0.f; check(gsdf_ba_energy(tSDF_->handle(), &E), "gsdf_ba_energy"); return E; }           /* .cpp:273 */
     void solveDist(float damping = 1.0f) { upload(); check(gsdf_ba_solve_dist(tSDF_->handle(), damping), "gsdf_ba_solve_dist"); }     /* .cpp:326 */
     void solvePose(float damping = 1.0f) { upload(); check(gsdf_ba_solve_pose(tSDF_->handle(), damping), "gsdf_ba_solve_pose"); download(); }   /* .cpp:499 */
+    /* the coupled step: one 6n x 6n system with the off-diagonal blocks the shared per-voxel mean creates -- .h:180, .cpp:392-496 */
+    void solvePoseFull(float damping = 1.0f) { upload(); check(gsdf_ba_solve_pose_full(tSDF_->handle(), damping), "gsdf_ba_solve_pose_full"); download(); }
     /* optimize() -- .cpp:611-662; returns the reference's bool (true = converged) */
     bool optimize(std::vector<float>* energies = nullptr) {
         upload();
         std::vector<float> e(2 * (size_t)settings_.max_it + 1);
         int ne = 0, conv = 0;
+        check(gsdf_ba_set_pose_step(tSDF_->handle(), (int)settings_.pose_step), "gsdf_ba_set_pose_step");   /* .cpp:627-628 */
         check(gsdf_ba_optimize(tSDF_->handle(), settings_.max_it, e.data(), &ne, &conv), "gsdf_ba_optimize");
         download();
         if (energies) energies->assign(e.begin(), e.begin() + ne);

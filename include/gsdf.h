@@ -249,6 +249,28 @@ int gsdf_ba_solve_pose(gsdf_ctx* c, float damping);
 int gsdf_ba_solve_dist(gsdf_ctx* c, float damping);
 int gsdf_ba_optimize(gsdf_ctx* c, int max_it, float* energies, int* n_energies, int* converged);
 int gsdf_ba_get_poses(gsdf_ctx* c, float* poses16_host);
+/* The coupled pose step -- solvePoseFull (PhotometricOptimizer.cpp:392-496, public at PhotometricOptimizer.h:180; optimize()
+ * names it as the alternative of solvePose at :627-628).  One 6n x 6n system over all keyframes instead of n systems of 6 x 6.
+ * For every voxel with |dist| <= voxel size (:406) the observations are collected exactly as in solvePose: the same visibility
+ * test, getIntensity, computeJc, the TRUNC_L2 rule (:435), A_ij, the 3 x 6 J_ij, N_j, inv_Nj = (float)(1. / (float)N_j), mean_j,
+ * r_ij = A_ij - mean_j.  Then
+ *     b[6i .. 6i+5]  += sum_c r_ij[c] * J_ij[c, :]                          (:461-462)
+ *     H[i, i]        += (1 - inv_Nj) * J_ij^T J_ij                          (:464-466)
+ *     H[i1, i2]      += (-inv_Nj) * J_i1j^T J_i2j,  i1 < i2 both counted by voxel j, and its transpose into H[i2, i1]   (:475-479)
+ * so the diagonal blocks and b are the decoupled step's sums (bit for bit what gsdf_ba_solve_pose solves) and only the
+ * off-diagonal blocks are new.  delta = H.ldlt().solve(b) (:483) is Eigen's LDLT: symmetric pivoting on the largest remaining
+ * |diagonal|, a zero pivot gives a zero component.  If any component of delta is NaN no pose moves (:488-490); otherwise
+ * t_i -= delta[6i .. 6i+2], R_i = R_i * SO3::exp(-delta[6i+3 .. 6i+5]) for every keyframe (:491-494).  damping is unused, as in
+ * the reference.  n is 1..64 as everywhere in gsdf_ba_*.
+ * gsdf_ba_pose_system assembles the system at the current state and changes nothing (poses, map, ColorUpsampler snapshot): H is
+ * (6n)^2 floats row-major, full and exactly symmetric, b is 6n floats; either may be NULL, both NULL is GSDF_ERR_INVALID.
+ * gsdf_ba_solve_pose_full assembles, solves and updates the poses; synchronous like gsdf_ba_solve_pose.
+ * gsdf_ba_set_pose_step chooses the pose step gsdf_ba_optimize runs at :627: 0 = solvePose (the default), 1 = solvePoseFull.
+ * It needs a gsdf_ba_setup (GSDF_ERR_INVALID otherwise, or for another value) and lasts until the next gsdf_ba_setup, which
+ * sets it back to 0. */
+int gsdf_ba_pose_system(gsdf_ctx* c, float* H, float* b);
+int gsdf_ba_solve_pose_full(gsdf_ctx* c, float damping);
+int gsdf_ba_set_pose_step(gsdf_ctx* c, int mode);
 /* what the last gsdf_ba_energy / gsdf_ba_solve_dist call (or the last energy sweep of gsdf_ba_optimize) counted: voxels that took
  * part (energy: |dist| <= voxel size, :285, seen by at least one keyframe; distance sweep: every voxel with an observation) and
  * observations (voxel x keyframe pairs that project into the image, :238-260) -- the units of the sweeps' algorithmic bytes

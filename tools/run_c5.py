@@ -5,6 +5,7 @@ Fuses a 640x480 S-tum stream at its ground-truth poses (1 cm voxels, trunc 10, v
 perturbs their poses, and times
   * gsdf_ba_optimize (PhotometricOptimizer::optimize, ps_optimizer/PhotometricOptimizer.cpp:611-662) end to end,
   * its three sweeps one by one (wall clock around the synchronous C-ABI entries, median of `--reps`),
+  * with `--pose-step full`: one coupled pose step (gsdf_ba_solve_pose_full, solvePoseFull :392-496) and optimize() with it,
   * the CPU oracle's optimize() FROM THE SAME STATE (same voxel values, same poses, same keyframes): `--oracle-it` iterations,
     1 core (the reference's PhotometricOptimizer is serial),
 and states the sweeps' algorithmic bytes: per sweep every existing voxel record is read once (32 B), every voxel that takes part
@@ -34,6 +35,8 @@ def main():
     ap.add_argument("--max-it", type=int, default=10)
     ap.add_argument("--oracle-it", type=int, default=1, help="iterations of the CPU oracle's optimize() timed from the same state (0 = skip)")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--pose-step", choices=["decoupled", "full"], default="decoupled",
+                    help="the pose step of optimize(): solvePose (:499-590) or the coupled solvePoseFull (:392-496); full also times one coupled step")
     args = ap.parse_args()
     import __graft_entry__ as graft
     pkg = graft.package()
@@ -65,6 +68,12 @@ def main():
     act, obs = g.ba_counters()
     t_pose = med(g.ba_solve_pose, 1)              # (moves the poses: once, then restored by the next setup)
     g.ba_setup(imgs, Pp, kf)
+    if args.pose_step == "full":
+        # one coupled step: pose sweep + the 6n x 6n contraction + its reduction, the host LDLT of the whole system, the pose upload
+        g.ba_pose_system()                        # (allocates the contraction's buffers: not part of a step)
+        t_system = med(g.ba_pose_system, args.reps)
+        t_pose_full = med(g.ba_solve_pose_full, 1)
+        g.ba_setup(imgs, Pp, kf)
     t_dist = med(g.ba_solve_dist, 1)
     act_d, obs_d = g.ba_counters()                # the distance sweep has no |dist| gate: every voxel with an observation
     b_energy = 32.0 * n_vox + 4.0 * vw * act + 48.0 * obs
@@ -81,22 +90,33 @@ def main():
                  "note": "all voxels (no |dist| gate, :326-388); its 144 B per observation are served by the caches for the most part (neighbouring voxels "
                          "sample neighbouring pixels of the same 50 images, 184 MB): the figure is an L2-side rate, not HBM traffic"},
     }
+    if args.pose_step == "full":
+        nk = int(len(kf)); nt = (6 * nk + 31) // 32
+        out["sweeps"]["pose_full"] = {"ms": round(t_pose_full * 1e3, 3), "system_ms": round(t_system * 1e3, 3), "columns": 6 * nk,
+                                      "rows": 3 * act, "padded_upper_triangle_entries": nt * (nt + 1) // 2 * 1024,
+                                      "contraction_flop": 2 * 3 * act * (nt * (nt + 1) // 2 * 1024),
+                                      "note": "ms: one gsdf_ba_solve_pose_full (assembly, download of H, host LDLT of 6n x 6n, pose upload); "
+                                              "system_ms: gsdf_ba_pose_system alone (assembly + download, median)"}
+    out["pose_step"] = args.pose_step
     # ---- optimize() end to end, from the perturbed poses on the fused map ----
     g.reset()
     for f in frames:
         g.update(*f)
     g.ba_setup(imgs, Pp, kf)
+    if args.pose_step == "full":
+        g.ba_set_pose_step(1)
+        g.ba_pose_system()                        # (the contraction's buffers are allocated by the first coupled call)
     g.sync()
     t0 = time.perf_counter(); conv, en = g.ba_optimize(args.max_it); t_opt = time.perf_counter() - t0
     Pn = g.ba_poses()
     steps = int(len(en) - 1)
     out["optimize"] = {"wall_s": round(t_opt, 4), "energy_evaluations": int(len(en)), "iterations": steps // 2, "converged": bool(conv),
                        "ms_per_iteration": round(t_opt * 1e3 / max(steps // 2, 1), 3),
-                       "E0": float(en[0]), "E_final": float(en[-1]),
+                       "E0": float(en[0]), "E_final": float(en[-1]), "energies": [float(e) for e in en],
                        "translation_err_before_m": float(np.abs(Pp[:, :3, 3] - P[:, :3, 3]).max()),
                        "translation_err_after_m": float(np.abs(Pn[:, :3, 3] - P[:, :3, 3]).max())}
     # ---- the CPU oracle from the same state ----
-    if args.oracle_it > 0:
+    if args.oracle_it > 0 and args.pose_step == "decoupled":      # (the oracle has no solvePoseFull)
         O = graft.oracle_module()
         o = O.Oracle(vs, T, W, H, seq.K)
         for f in frames:
