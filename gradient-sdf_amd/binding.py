@@ -171,6 +171,8 @@ def load(path=None):
         "gsdf_raycast": (C.c_int, [vp, fp, fp, fp, C.c_int, C.c_int, C.c_float, C.c_float, fp, fp]),
         "gsdf_extract_mesh": (C.c_int, [vp, C.c_float, C.POINTER(C.c_int8), fp, C.c_int64, C.POINTER(C.c_int64)]),
         "gsdf_extract_mesh_indexed": (C.c_int, [vp, C.c_float, C.POINTER(C.c_int8), fp, fp, i32p, C.c_int64, C.c_int64, i64p, i64p]),
+        "gsdf_gradient_angles": (C.c_int, [vp, fp, C.c_int, i32p, fp, C.c_int64, i64p]),
+        "gsdf_gradient_stats": (C.c_int, [vp, fp, C.c_int, fp, C.c_int, C.POINTER(C.c_double)]),
         "gsdf_dev_alloc": (C.c_int, [vp, C.POINTER(vp), C.c_int64]),
         "gsdf_dev_free": (C.c_int, [vp, vp]),
         "gsdf_dev_upload": (C.c_int, [vp, vp, vp, C.c_int64]),
@@ -212,7 +214,7 @@ ABI_SYMBOLS = [
     "gsdf_merge_allreduce", "gsdf_merge_allreduce_with", "gsdf_rccl_unique_id", "gsdf_rccl_comm_init", "gsdf_rccl_comm_count",
     "gsdf_rccl_comm_destroy",
     "gsdf_query", "gsdf_get_voxels", "gsdf_raycast", "gsdf_raycast_dev", "gsdf_raycast_counters", "gsdf_extract_mesh",
-    "gsdf_extract_mesh_indexed",
+    "gsdf_extract_mesh_indexed", "gsdf_gradient_angles", "gsdf_gradient_stats",
     "gsdf_dev_alloc", "gsdf_dev_free", "gsdf_dev_upload", "gsdf_dev_download", "gsdf_timer_start", "gsdf_timer_stop_ms",
     "gsdf_host_alloc", "gsdf_host_free", "gsdf_dev_upload_async", "gsdf_mark", "gsdf_mark_wait", "gsdf_mark_reached",
     "gsdf_dev_upload_ahead", "gsdf_upload_wait",
@@ -745,6 +747,29 @@ class GradSdf:
             self._chk(self.L.gsdf_extract_mesh_indexed(self.h, C.c_float(iso), tp, _fp(V), _fp(N), F.ctypes.data_as(C.POINTER(C.c_int32)),
                                                        nv.value, nf.value, C.byref(nv), C.byref(nf)))
         return V[:nv.value], N[:nv.value], F[:nf.value]
+
+    def gradient_angles(self, spheres):
+        """gsdf_gradient_angles: (keys int32 [n, 3], rows float32 [n, 5]) -- per voxel dist and the angle in degrees between
+        the analytic gradient of the sphere scene `spheres` (rows cx cy cz R) and the stored / central / forward / backward
+        estimate; NaN = undefined; gsdf_export's sorted order (include/gsdf.h)."""
+        sp = np.ascontiguousarray(spheres, dtype=np.float32).reshape(-1, 4)
+        n = C.c_int64(0)
+        self._chk(self.L.gsdf_gradient_angles(self.h, _fp(sp), len(sp), None, None, 0, C.byref(n)))
+        keys = np.empty((max(n.value, 1), 3), np.int32)
+        rows = np.empty((max(n.value, 1), 5), np.float32)
+        if n.value:
+            self._chk(self.L.gsdf_gradient_angles(self.h, _fp(sp), len(sp), keys.ctypes.data_as(C.POINTER(C.c_int32)), _fp(rows),
+                                                  n.value, C.byref(n)))
+        return keys[:n.value], rows[:n.value]
+
+    def gradient_stats(self, spheres, thresholds):
+        """gsdf_gradient_stats: float64 [4, n_thr, 5] = count, mean, median, rmse, p95 of those angles over fabsf(dist) < d[k],
+        for the stored, central, forward and backward estimators."""
+        sp = np.ascontiguousarray(spheres, dtype=np.float32).reshape(-1, 4)
+        thr = np.ascontiguousarray(thresholds, dtype=np.float32).reshape(-1)
+        out = np.empty((4, len(thr), 5), np.float64)
+        self._chk(self.L.gsdf_gradient_stats(self.h, _fp(sp), len(sp), _fp(thr), len(thr), out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
 
     # -- timing -------------------------------------------------------------------------------
     def timer_start(self):

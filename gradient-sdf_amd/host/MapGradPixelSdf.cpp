@@ -138,3 +138,11 @@ bool MapGradPixelSdf::extract_pc(std::string filename) { return gsdf_exports::wr
 bool MapGradPixelSdf::save_sdf(std::string filename) { return gsdf_exports::write_sdf_txt(ctx_, voxel_size_, filename); }
 bool MapGradPixelSdf::extract_mesh(std::string filename) { return gsdf_exports::write_mesh_ply(ctx_, voxel_size_, filename, nullptr); }
 bool MapGradPixelSdf::extract_mesh_indexed(std::string filename) { return gsdf_exports::write_indexed_mesh_ply(ctx_, filename, nullptr, nullptr); }
+bool MapGradPixelSdf::gradient_analysis(const std::vector<float>& spheres4, const std::vector<float>& thresholds, std::vector<double>& stats) const {
+    if (spheres4.empty() || spheres4.size() % 4 != 0 || thresholds.empty()) return false;
+    stats.assign(4 * thresholds.size() * 5, 0.0);
+    return gsdf_gradient_stats(ctx_, spheres4.data(), (int)(spheres4.size() / 4), thresholds.data(), (int)thresholds.size(), stats.data()) == GSDF_OK;
+}
+bool MapGradPixelSdf::save_gradient_analysis(const std::vector<float>& spheres4, const std::vector<float>& thresholds, std::string filename) const {
+    return gsdf_exports::write_gradient_stats_txt(ctx_, spheres4, thresholds, filename);
+}

@@ -59,12 +59,19 @@ public:
     /* the same surface as an indexed mesh with a gradient normal per vertex, binary PLY (gsdf_extract_mesh_indexed; not in the
      * reference).  MapPixelSdf inherits it: a base context stores the same gradient sums */
     bool extract_mesh_indexed(std::string filename);
+    /* the gradient-accuracy table of a sphere scene (gsdf_gradient_stats; matlab/GradientAnalysisSpheres.m, phi_statistics.m):
+     * spheres4 = rows cx cy cz R, thresholds ascending; stats = [4 estimators][thresholds][count, mean, median, rmse, p95].
+     * false when the library refuses the arguments.  MapPixelSdf inherits it */
+    bool gradient_analysis(const std::vector<float>& spheres4, const std::vector<float>& thresholds, std::vector<double>& stats) const;
+    /* ... written as text (gsdf_exports::write_gradient_stats_txt) */
+    bool save_gradient_analysis(const std::vector<float>& spheres4, const std::vector<float>& thresholds, std::string filename) const;
 
     /* fix the frame size / intrinsics / normal-estimator window before driving the *_dev entries directly (update() does
      * it on the first frame) */
     void prepare(int W, int H, const Mat3f& K, NormalEstimator* NEst);
     gsdf_ctx* handle() const { return ctx_; }
     float voxel_size() const { return voxel_size_; }
+    float trunc_dist() const { return T_; }
 
 protected:
     /* a context of another map type (gsdf_set_map_type): MapPixelSdf */

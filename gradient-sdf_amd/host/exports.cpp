@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <cstdio>
 #include <fstream>
 #include <iostream>
 #include <limits>
@@ -135,6 +136,33 @@ bool write_indexed_mesh_ply(gsdf_ctx* ctx, const std::string& filename, long* n_
     if (n_vertices) *n_vertices = (long)nv;
     if (n_faces) *n_faces = (long)nf;
     return MarchingCubes::saveIndexedPly(filename, v, n, f);
+}
+
+std::vector<float> gradient_ladder(float trunc_dist) {
+    const long n = (long)std::floor((double)trunc_dist / 0.001 + 1e-3);
+    std::vector<float> d;
+    for (long k = 1; k <= n; ++k) d.push_back((float)((double)k * 0.001));
+    return d;
+}
+
+bool write_gradient_stats_txt(gsdf_ctx* ctx, const std::vector<float>& spheres4, const std::vector<float>& thresholds,
+                              const std::string& filename) {
+    static const char* const names[4] = { "stored", "central", "forward", "backward" };
+    const size_t nt = thresholds.size();
+    std::vector<double> st(4 * nt * 5);
+    if (spheres4.empty() || spheres4.size() % 4 != 0 || nt == 0) return false;
+    if (gsdf_gradient_stats(ctx, spheres4.data(), (int)(spheres4.size() / 4), thresholds.data(), (int)nt, st.data()) != GSDF_OK) return false;
+    FILE* f = std::fopen(filename.c_str(), "w");
+    if (!f) return false;
+    std::fprintf(f, "# angle to the analytic gradient in degrees, voxels with |dist| < d: d count mean median rmse p95\n");
+    for (size_t e = 0; e < 4; ++e) {
+        std::fprintf(f, "# estimator %zu %s\n", e, names[e]);
+        for (size_t k = 0; k < nt; ++k) {
+            const double* r = &st[(e * nt + k) * 5];
+            std::fprintf(f, "%.9g %lld %.17g %.17g %.17g %.17g\n", (double)thresholds[k], (long long)r[0], r[1], r[2], r[3], r[4]);
+        }
+    }
+    return std::fclose(f) == 0;
 }
 
 } // namespace gsdf_exports

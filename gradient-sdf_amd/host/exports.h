@@ -6,6 +6,7 @@
 #define GSDF_HOST_EXPORTS_H_
 
 #include <string>
+#include <vector>
 
 #include "../../include/gsdf.h"
 
@@ -21,6 +22,13 @@ bool write_mesh_ply(gsdf_ctx* ctx, float voxel_size, const std::string& filename
 /* the same surface as an indexed mesh with gradient normals (gsdf_extract_mesh_indexed; not in the reference), binary PLY
  * (MarchingCubes::saveIndexedPly); *n_vertices / *n_faces (nullable) = what was written.  false for an empty mesh, like write_mesh_ply */
 bool write_indexed_mesh_ply(gsdf_ctx* ctx, const std::string& filename, long* n_vertices, long* n_faces);
+/* the thresholds of matlab/GradientAnalysisSpheres.m:155, d = 0.001 : 0.001 : trunc_dist, as floats; the count forgives the
+ * float rounding of trunc_dist by a thousandth of a step (5 voxels of 0.02 m are 0.099999994: 100 thresholds) */
+std::vector<float> gradient_ladder(float trunc_dist);
+/* the gradient-accuracy table (gsdf_gradient_stats; matlab/phi_statistics.m) as text: one block per estimator (stored,
+ * central, forward, backward) behind a `# estimator` line, rows `d count mean median rmse p95`; spheres4 = rows cx cy cz R */
+bool write_gradient_stats_txt(gsdf_ctx* ctx, const std::vector<float>& spheres4, const std::vector<float>& thresholds,
+                              const std::string& filename);
 }
 
 #endif

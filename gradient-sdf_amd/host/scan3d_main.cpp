@@ -19,6 +19,11 @@
  *   --transport shm   the exchange through host shared memory instead of RCCL: N ranks on ONE device (test boxes).
  *   --mesh-indexed    additionally write <results>mesh_indexed.ply: the same surface with one vertex per crossed grid edge,
  *                     faces as indices and gradient normals, binary PLY (gsdf_extract_mesh_indexed);
+ *   --gradient-analysis <spheres.txt>
+ *                     after the other exports write <results>gradient_sdf_gradient_stats.txt: the angle between the stored /
+ *                     central / forward / backward gradient and the analytic one of the sphere scene in the file (rows
+ *                     cx cy cz R), as count, mean, median, rmse and 95th percentile over |dist| < d for the ladder
+ *                     d = 0.001 : 0.001 : trunc of matlab/GradientAnalysisSpheres.m (gsdf_gradient_stats);
  * --scan-type grad-sdf (MapGradPixelSdf) or base-sdf (MapPixelSdf, the plain-SDF baseline, :99-114 / :226-233); base-sdf runs
  * on one GPU only (--gpus N > 1 refuses it).
  */
@@ -41,6 +46,7 @@
 #include "MapPixelSdf.h"
 #include "RigidOptimizer.h"
 #include "Timer.h"
+#include "exports.h"
 #include "frame_pipeline.h"
 #include "img_loader.h"
 #include "shm_collective.h"
@@ -54,7 +60,7 @@ struct Options {
     int width = 640, height = 480, capacity_log2 = 22, device = 0;
     int max_capacity_log2 = 28;          /* the table doubles by itself up to this (the reference's map has no capacity) */
     int gpus = 1, rank = -1, decode_threads = 0;
-    std::string transport = "rccl", rendezvous;
+    std::string transport = "rccl", rendezvous, gradient_spheres;
 };
 
 bool parse(int argc, char** argv, Options& o) {
@@ -68,7 +74,7 @@ bool parse(int argc, char** argv, Options& o) {
         if (a == "-h" || a == "--help") {
             std::cout << "Hash Table-Based 3D Scanning (MI355X)\n  --input --results --pose-file --first --last --scan-type"
                          " --data-type --voxel-size --trunc --save-sdf --width --height --hash-capacity --hash-max-capacity --device"
-                         " --sync --decode-threads --gpus --transport rccl|shm --mesh-indexed\n"
+                         " --sync --decode-threads --gpus --transport rccl|shm --mesh-indexed --gradient-analysis <spheres.txt>\n"
                          "  --scan-type grad-sdf|base-sdf (base-sdf: one GPU only, --gpus 1)\n";
             std::exit(0);
         }
@@ -92,6 +98,7 @@ bool parse(int argc, char** argv, Options& o) {
         else if (a == "--rendezvous") o.rendezvous = v;                /* set by the launcher */
         else if (a == "--transport") o.transport = v;
         else if (a == "--decode-threads") o.decode_threads = std::stoi(v);
+        else if (a == "--gradient-analysis") o.gradient_spheres = v;
         else { std::cerr << "unknown option " << a << std::endl; return false; }
     }
     return true;
@@ -457,6 +464,22 @@ int run(int, char**, Options& opt) {
         T.tic();
         if (!tSDF->save_sdf(opt.output + prefix)) std::cerr << "could not save voxel grid info file " << opt.output + prefix << "!" << std::endl;
         T.toc("Save sdf txt files to disk");
+    }
+    if (!opt.gradient_spheres.empty()) {
+        T.tic();
+        std::vector<float> spheres;
+        std::ifstream sf(opt.gradient_spheres);
+        for (float v; sf >> v;) spheres.push_back(v);
+        const std::vector<float> d = gsdf_exports::gradient_ladder(tSDF->trunc_dist());
+        filename = opt.output + prefix + "_gradient_stats.txt";
+        if (d.size() > 256)
+            std::cerr << "Gradient analysis skipped: the ladder 0.001 : 0.001 : " << tSDF->trunc_dist() << " of GradientAnalysisSpheres.m has "
+                      << d.size() << " thresholds and does not fit the library's limit of 256 thresholds." << std::endl;
+        else if (spheres.empty() || spheres.size() % 4 != 0)
+            std::cerr << "Could not read rows cx cy cz R from " << opt.gradient_spheres << "!" << std::endl;
+        else if (!tSDF->save_gradient_analysis(spheres, d, filename))
+            std::cerr << "Could not save gradient statistics to " << filename << ": " << gsdf_last_error() << std::endl;
+        T.toc("Save gradient statistics to disk");
     }
     return 0;
 }

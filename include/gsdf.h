@@ -489,6 +489,46 @@ int gsdf_extract_mesh_indexed(gsdf_ctx* c, float iso, const int8_t tri_table[256
                               int32_t* faces_out /* 3 per face */, int64_t max_vertices, int64_t max_faces,
                               int64_t* n_vertices, int64_t* n_faces);
 
+/* GRADIENT ACCURACY on a sphere scene: the angle between a voxel's gradient and the analytic one, for the gradient the map
+ * STORES and for finite differences of the stored distances, and its statistics over the voxels near the surface -- the paper's
+ * central measurement (matlab/GradientAnalysisSpheres.m, matlab/phi_statistics.m), on the map in HBM instead of save_sdf's text
+ * files.  All arithmetic is DOUBLE unless stated; its inputs are the floats the map holds.
+ *  - Voxels and grid: a voxel exists iff w > 0.  dist is bit for bit gsdf_export(raw_sums = 0)'s; g^_1 is the stored gradient
+ *    sum, normalised (:59-75).  D(v) = dist of an existing voxel, else the context's trunc_dist (D = vs*T*ones(sz), :55); a
+ *    neighbour outside the packable key range is missing.  The grid is the bounding box of all existing voxels (save_sdf's
+ *    `voxel min` / `voxel max`, copied in :48-50).
+ *  - Estimators, per existing voxel, each normalised (a zero or non-finite vector: NaN):
+ *      0 stored    g^_1 (:59-75)
+ *      1 central   gradient(D, vs) (:81-87), per axis (D[i+1] - D[i-1]) / (2 vs) inside the box, (D[i+1] - D[i]) / vs on the box's
+ *                  minimal face, (D[i] - D[i-1]) / vs on its maximal face, 0 where the box is one voxel thick on that axis
+ *      2 forward   vs_inv (D[i+1] - D[i]), 0 on the maximal face (:117-130)
+ *      3 backward  vs_inv (D[i] - D[i-1]), 0 on the minimal face (:136-149)
+ *    with vs the context's voxel size widened to double and vs_inv = 1 / vs.
+ *  - Ground truth (:96-111): the voxel centre c = vs * (float)idx, a float product as the project forms voxel centres, widened
+ *    to double; n_spheres rows cx cy cz R; the sphere maximising R - |c - centre| (the first among equals) gives
+ *    g = normalized(c - centre) (NaN for a voxel centre on a sphere centre: all four angles undefined).
+ *  - Angle (:162-163): phi_e = acosd(min(|g^_e . g|, 1)), stored as float32 degrees; NaN marks an undefined estimator.
+ *  - Statistics (phi_statistics.m:69-73) for ascending thresholds d[0..n_thr): over the voxels with fabsf(dist) < d[k] (a float
+ *    compare) and phi_e not NaN: count, mean, rmse = sqrt(mean(phi^2)), median and 95th percentile of the float32 phi values,
+ *    in double.  Percentiles are MATLAB's prctile: for sorted x[1..n] the position n p / 100 + 0.5, clamped to [1, n], linear in
+ *    between (numpy's method="hazen").  An empty subset gives count 0 and NaN for the rest.
+ * Stated deviations: the script reads 6-digit text and takes vs*T in double, here the map's own floats and trunc_dist are used;
+ * phi_statistics' hist2d output and the plots are not part of this.
+ * Conventions: max_n = 0 (keys and rows5 may be NULL) sizes the output; a buffer that is too small: nothing is written,
+ * GSDF_ERR_INVALID, the need in *n; an empty map gives *n = 0 / count 0 with NaN, GSDF_OK.  GSDF_ERR_INVALID with nothing
+ * written: n_spheres outside 1..64, n_thr outside 1..256, thresholds that are not finite, not positive or not strictly
+ * ascending, a sphere row that is not finite or has R <= 0, NULL inputs.  Synchronous.  The table is only read: the map, a
+ * ColorUpsampler snapshot and PhotoBA state stay as they are; a waiting pipelined fusion is launched first.  Base-sdf contexts
+ * are accepted (they store the same sums).  At most 2^31 - 1 voxels.
+ * Deterministic: no floating-point atomics, every sum taken in one fixed order over sorted arrays -- the same map gives the
+ * same bytes, run to run and across gsdf_grow. */
+/* rows5 per voxel: dist, phi[4] (degrees; NaN = undefined); rows and keys in the order of gsdf_export(sorted = 1) */
+int gsdf_gradient_angles(gsdf_ctx* c, const float* spheres4_host, int n_spheres,
+                         int32_t* keys, float* rows5, int64_t max_n, int64_t* n);
+/* stats: 4 x n_thr x 5 doubles = count, mean, median, rmse, p95; estimator order as above */
+int gsdf_gradient_stats(gsdf_ctx* c, const float* spheres4_host, int n_spheres,
+                        const float* thresholds, int n_thr, double* stats);
+
 /* device-memory plumbing so callers can stage frames in HBM without another runtime */
 int gsdf_dev_alloc(gsdf_ctx* c, void** dev_ptr, int64_t bytes);
 int gsdf_dev_free(gsdf_ctx* c, void* dev_ptr);          /* withdraws a next-frame hint that lies in the freed allocation */
