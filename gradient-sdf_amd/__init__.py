@@ -11,4 +11,4 @@ The directory name contains a hyphen (task contract); import it through
 ``__graft_entry__.package()`` which registers it as ``gradient_sdf_amd``.
 """
 from . import binding, parallel, synth  # noqa: F401
-from .binding import MAP_BASE, MAP_GRAD, GradSdf, GsdfError  # noqa: F401
+from .binding import MAP_BASE, MAP_GRAD, MESH_KEEP_LARGEST, GradSdf, GsdfError  # noqa: F401

@@ -24,6 +24,7 @@ TEST_LIB_PATH = os.environ.get("GSDF_TEST_LIB", os.path.join(CSRC, "libgsdf_test
 
 GSDF_OK, ERR_TABLE_FULL, ERR_KEY_RANGE, ERR_INVALID, ERR_HIP, ERR_NO_DEVICE = 0, 1, 2, 3, 4, 5
 MAP_GRAD, MAP_BASE = 0, 1                                     # gsdf_set_map_type (include/gsdf.h)
+MESH_KEEP_LARGEST = -1                                        # gsdf_extract_mesh_indexed_filtered's min_faces (GSDF_MESH_KEEP_LARGEST)
 
 
 class GsdfError(RuntimeError):
@@ -171,6 +172,10 @@ def load(path=None):
         "gsdf_raycast": (C.c_int, [vp, fp, fp, fp, C.c_int, C.c_int, C.c_float, C.c_float, fp, fp]),
         "gsdf_extract_mesh": (C.c_int, [vp, C.c_float, C.POINTER(C.c_int8), fp, C.c_int64, C.POINTER(C.c_int64)]),
         "gsdf_extract_mesh_indexed": (C.c_int, [vp, C.c_float, C.POINTER(C.c_int8), fp, fp, i32p, C.c_int64, C.c_int64, i64p, i64p]),
+        "gsdf_mesh_components": (C.c_int, [vp, C.c_float, C.POINTER(C.c_int8), i32p, i32p, C.c_int64, C.c_int64, i32p, fp, C.c_int64,
+                                           i64p, i64p, i64p]),
+        "gsdf_extract_mesh_indexed_filtered": (C.c_int, [vp, C.c_float, C.POINTER(C.c_int8), C.c_int64, fp, fp, i32p, C.c_int64, C.c_int64,
+                                                         i64p, i64p, i64p, i64p]),
         "gsdf_gradient_angles": (C.c_int, [vp, fp, C.c_int, i32p, fp, C.c_int64, i64p]),
         "gsdf_gradient_stats": (C.c_int, [vp, fp, C.c_int, fp, C.c_int, C.POINTER(C.c_double)]),
         "gsdf_dev_alloc": (C.c_int, [vp, C.POINTER(vp), C.c_int64]),
@@ -214,7 +219,7 @@ ABI_SYMBOLS = [
     "gsdf_merge_allreduce", "gsdf_merge_allreduce_with", "gsdf_rccl_unique_id", "gsdf_rccl_comm_init", "gsdf_rccl_comm_count",
     "gsdf_rccl_comm_destroy",
     "gsdf_query", "gsdf_get_voxels", "gsdf_raycast", "gsdf_raycast_dev", "gsdf_raycast_counters", "gsdf_extract_mesh",
-    "gsdf_extract_mesh_indexed", "gsdf_gradient_angles", "gsdf_gradient_stats",
+    "gsdf_extract_mesh_indexed", "gsdf_mesh_components", "gsdf_extract_mesh_indexed_filtered", "gsdf_gradient_angles", "gsdf_gradient_stats",
     "gsdf_dev_alloc", "gsdf_dev_free", "gsdf_dev_upload", "gsdf_dev_download", "gsdf_timer_start", "gsdf_timer_stop_ms",
     "gsdf_host_alloc", "gsdf_host_free", "gsdf_dev_upload_async", "gsdf_mark", "gsdf_mark_wait", "gsdf_mark_reached",
     "gsdf_dev_upload_ahead", "gsdf_upload_wait",
@@ -747,6 +752,44 @@ class GradSdf:
             self._chk(self.L.gsdf_extract_mesh_indexed(self.h, C.c_float(iso), tp, _fp(V), _fp(N), F.ctypes.data_as(C.POINTER(C.c_int32)),
                                                        nv.value, nf.value, C.byref(nv), C.byref(nf)))
         return V[:nv.value], N[:nv.value], F[:nf.value]
+
+    def mesh_components(self, iso=0.0, tri_table=None):
+        """gsdf_mesh_components: (vertex_comp int32 [nv], face_comp int32 [nf], counts int32 [C, 2] = faces, vertices,
+        bbox float32 [C, 6] = min xyz, max xyz) -- the connected components of extract_mesh_indexed's mesh, ids in ascending
+        order of a component's smallest vertex id (include/gsdf.h)."""
+        tp = None
+        if tri_table is not None:
+            tt = np.ascontiguousarray(tri_table, dtype=np.int8).reshape(256 * 16)
+            tp = tt.ctypes.data_as(C.POINTER(C.c_int8))
+        i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))                 # noqa: E731
+        nv, nf, nc = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self.L.gsdf_mesh_components(self.h, C.c_float(iso), tp, None, None, 0, 0, None, None, 0, C.byref(nv), C.byref(nf), C.byref(nc)))
+        vc = np.empty(max(nv.value, 1), np.int32)
+        fc = np.empty(max(nf.value, 1), np.int32)
+        counts = np.empty((max(nc.value, 1), 2), np.int32)
+        bbox = np.empty((max(nc.value, 1), 6), np.float32)
+        if nf.value:
+            self._chk(self.L.gsdf_mesh_components(self.h, C.c_float(iso), tp, i32(vc), i32(fc), nv.value, nf.value, i32(counts), _fp(bbox),
+                                                  nc.value, C.byref(nv), C.byref(nf), C.byref(nc)))
+        return vc[:nv.value], fc[:nf.value], counts[:nc.value], bbox[:nc.value]
+
+    def extract_mesh_indexed_filtered(self, min_faces, iso=0.0, tri_table=None):
+        """gsdf_extract_mesh_indexed_filtered: (V, N, F, n_components, n_kept) -- extract_mesh_indexed without the components of
+        fewer than min_faces faces, or with min_faces = MESH_KEEP_LARGEST the largest component alone (include/gsdf.h)."""
+        tp = None
+        if tri_table is not None:
+            tt = np.ascontiguousarray(tri_table, dtype=np.int8).reshape(256 * 16)
+            tp = tt.ctypes.data_as(C.POINTER(C.c_int8))
+        nv, nf, nc, nk = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        ref = (C.byref(nv), C.byref(nf), C.byref(nc), C.byref(nk))
+        self._chk(self.L.gsdf_extract_mesh_indexed_filtered(self.h, C.c_float(iso), tp, int(min_faces), None, None, None, 0, 0, *ref))
+        V = np.empty((max(nv.value, 1), 3), np.float32)
+        N = np.empty((max(nv.value, 1), 3), np.float32)
+        F = np.empty((max(nf.value, 1), 3), np.int32)
+        if nf.value:
+            self._chk(self.L.gsdf_extract_mesh_indexed_filtered(self.h, C.c_float(iso), tp, int(min_faces), _fp(V), _fp(N),
+                                                                F.ctypes.data_as(C.POINTER(C.c_int32)), nv.value, nf.value, *ref))
+        return V[:nv.value], N[:nv.value], F[:nf.value], nc.value, nk.value
 
     def gradient_angles(self, spheres):
         """gsdf_gradient_angles: (keys int32 [n, 3], rows float32 [n, 5]) -- per voxel dist and the angle in degrees between

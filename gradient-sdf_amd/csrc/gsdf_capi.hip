@@ -1711,7 +1711,93 @@ int gsdf_extract_mesh(gsdf_ctx* c, float iso, const int8_t tri_table[256 * 16], 
 /* The steps are listed at the head of gsdf_mesh_index.hip.  The counting pass is gsdf_extract_mesh's own sizing pass (k_mesh_bbox
  * + k_mesh with no room): it leaves the bounding-box minimum on the device and the triangle count, so the corner pass runs once,
  * into buffers of the exact size, whatever the caller's maxima are -- the vertex count is known only after the weld, and it is
- * reported also when the caller's buffers are too small. */
+ * reported also when the caller's buffers are too small.
+ *
+ * indexed_mesh_dev is the device part, shared by gsdf_extract_mesh_indexed and the entries that work on the welded arrays
+ * (gsdf_mesh_components, gsdf_extract_mesh_indexed_filtered): indexed_mesh_count runs up to the vertex count and synchronises,
+ * indexed_mesh_weld enqueues the weld and the normals and leaves faces / v / n on the device. */
+namespace {
+struct indexed_mesh_dev {
+    gsdf_dev<int> mn;
+    gsdf_dev<signed char> tab;
+    gsdf_dev<float> tris, v, n;
+    gsdf_dev<unsigned long long> keys, keys2, ekeys, ck, ck2, vkeys;
+    gsdf_dev<uint32_t> muw, idx, order, rank, rank2, heads, before, vmuw;
+    gsdf_dev<int32_t> faces;
+    gsdf_dev<void> tmp;
+    size_t nt = 0, nc = 0, nv = 0;                             /* faces, corners, vertices */
+};
+
+int indexed_mesh_count(gsdf_ctx* c, float iso, const int8_t* tri_table, const char* who, indexed_mesh_dev& m) {
+    m.nt = m.nc = m.nv = 0;
+    HIP_TRY(m.mn.alloc(3));
+    HIP_TRY(m.tab.alloc(256 * 16));
+    const int big[3] = { 2147483647, 2147483647, 2147483647 };
+    HIP_TRY(hipMemcpyAsync(m.mn, big, sizeof(big), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(m.tab, tri_table, 256 * 16, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream));
+    unsigned long long n = 0, n2 = 0;
+    gsdf_launch_mesh(c->stream, c->tab, c->n_slots, c->voxel_size, iso, m.mn, m.tab, nullptr, nullptr, c->counter, 0);
+    HIP_TRY(hipMemcpyAsync(&n, c->counter, sizeof(n), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (n == 0) return GSDF_OK;
+    if (n > 2147483647ull / 3)
+        return fail(GSDF_ERR_INVALID, std::string(who) + ": more than (2^31 - 1) / 3 triangles (vertex ids and corner ranks are 32-bit)");
+    const size_t nt = (size_t)n, nc = 3 * nt;
+    HIP_TRY(m.tris.alloc(nt * 9));
+    HIP_TRY(m.keys.alloc(nt));
+    HIP_TRY(m.keys2.alloc(nt));
+    HIP_TRY(m.ekeys.alloc(nc));
+    HIP_TRY(m.muw.alloc(nc));
+    HIP_TRY(m.idx.alloc(nt));
+    HIP_TRY(m.order.alloc(nt));
+    HIP_TRY(m.ck.alloc(nc));
+    HIP_TRY(m.ck2.alloc(nc));
+    HIP_TRY(m.rank.alloc(nc));
+    HIP_TRY(m.rank2.alloc(nc));
+    HIP_TRY(m.heads.alloc(nc));
+    HIP_TRY(m.before.alloc(nc));
+    size_t b0 = 0, b1 = 0, b2 = 0;
+    HIP_TRY(gsdf_sort_pairs_u64(nullptr, &b0, m.keys, m.keys2, m.idx, m.order, nt, c->stream));
+    HIP_TRY(gsdf_sort_pairs_u64(nullptr, &b1, m.ck, m.ck2, m.rank, m.rank2, nc, c->stream));
+    HIP_TRY(gsdf_run_heads_scan(nullptr, &b2, m.ck2, m.heads, m.before, nc, c->stream));
+    HIP_TRY(m.tmp.alloc(std::max<size_t>(std::max(b0, b1), std::max<size_t>(b2, 8))));
+    HIP_TRY(hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream));
+    gsdf_launch_mesh_corners(c->stream, c->tab, c->n_slots, c->voxel_size, iso, m.mn, m.tab, m.tris, m.keys, m.ekeys, m.muw, c->counter,
+                             (long long)nt);
+    HIP_TRY(hipMemcpyAsync(&n2, c->counter, sizeof(n2), hipMemcpyDeviceToHost, c->stream));
+    /* the soup's order, then the weld: stable sort of (edge key, corner rank), run starts, their scan */
+    gsdf_launch_iota(c->stream, m.idx, nt);
+    b0 = m.tmp.bytes();
+    HIP_TRY(gsdf_sort_pairs_u64(m.tmp, &b0, m.keys, m.keys2, m.idx, m.order, nt, c->stream));
+    gsdf_launch_corner_keys(c->stream, m.ekeys, m.order, m.ck, m.rank, nt);
+    b1 = m.tmp.bytes();
+    HIP_TRY(gsdf_sort_pairs_u64(m.tmp, &b1, m.ck, m.ck2, m.rank, m.rank2, nc, c->stream));
+    b2 = m.tmp.bytes();
+    HIP_TRY(gsdf_run_heads_scan(m.tmp, &b2, m.ck2, m.heads, m.before, nc, c->stream));
+    uint32_t last[2] = { 0u, 0u };
+    HIP_TRY(hipMemcpyAsync(&last[0], m.before + (nc - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&last[1], m.heads + (nc - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (n2 != n) return fail(GSDF_ERR_HIP, std::string(who) + ": the map changed between the counting and the corner pass");
+    m.nt = nt; m.nc = nc; m.nv = (size_t)last[0] + last[1];
+    return GSDF_OK;
+}
+
+int indexed_mesh_weld(gsdf_ctx* c, bool normals, indexed_mesh_dev& m) {
+    HIP_TRY(m.faces.alloc(m.nc));
+    HIP_TRY(m.v.alloc(m.nv * 3));
+    HIP_TRY(m.vkeys.alloc(m.nv));
+    HIP_TRY(m.vmuw.alloc(m.nv));
+    if (normals) HIP_TRY(m.n.alloc(m.nv * 3));
+    gsdf_launch_weld(c->stream, m.ck2, m.rank2, m.heads, m.before, m.order, m.tris, m.muw, m.nc, m.faces, m.v, m.vkeys, m.vmuw);
+    if (normals) gsdf_launch_vertex_normals(c->stream, c->tab, m.mn, m.vkeys, m.vmuw, m.nv, m.n);
+    HIP_TRY(hipGetLastError());
+    return GSDF_OK;
+}
+} // namespace
+
 int gsdf_extract_mesh_indexed(gsdf_ctx* c, float iso, const int8_t tri_table[256 * 16], float* vertices_out, float* normals_out,
                               int32_t* faces_out, int64_t max_vertices, int64_t max_faces, int64_t* n_vertices, int64_t* n_faces) {
     GSDF_FLUSH(c);
@@ -1720,83 +1806,156 @@ int gsdf_extract_mesh_indexed(gsdf_ctx* c, float iso, const int8_t tri_table[256
     if (!tri_table) tri_table = GSDF_MC_TRI_TABLE;
     HIP_TRY(hipSetDevice(c->device));
     *n_vertices = 0; *n_faces = 0;
-    gsdf_dev<int> d_mn;
-    gsdf_dev<signed char> d_tab;
-    HIP_TRY(d_mn.alloc(3));
-    HIP_TRY(d_tab.alloc(256 * 16));
-    const int big[3] = { 2147483647, 2147483647, 2147483647 };
-    HIP_TRY(hipMemcpyAsync(d_mn, big, sizeof(big), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_tab, tri_table, 256 * 16, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream));
-    unsigned long long n = 0, n2 = 0;
-    gsdf_launch_mesh(c->stream, c->tab, c->n_slots, c->voxel_size, iso, d_mn, d_tab, nullptr, nullptr, c->counter, 0);
-    HIP_TRY(hipMemcpyAsync(&n, c->counter, sizeof(n), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (n == 0) return GSDF_OK;
-    if (n > 2147483647ull / 3)
-        return fail(GSDF_ERR_INVALID, "gsdf_extract_mesh_indexed: more than (2^31 - 1) / 3 triangles (vertex ids and corner ranks are 32-bit)");
-    const size_t nt = (size_t)n, nc = 3 * nt;
-    gsdf_dev<float> d_tris;
-    gsdf_dev<unsigned long long> d_keys, d_keys2, d_ekeys, d_ck, d_ck2;
-    gsdf_dev<uint32_t> d_muw, d_idx, d_order, d_rank, d_rank2, d_heads, d_before;
-    gsdf_dev<void> d_tmp;
-    HIP_TRY(d_tris.alloc(nt * 9));
-    HIP_TRY(d_keys.alloc(nt));
-    HIP_TRY(d_keys2.alloc(nt));
-    HIP_TRY(d_ekeys.alloc(nc));
-    HIP_TRY(d_muw.alloc(nc));
-    HIP_TRY(d_idx.alloc(nt));
-    HIP_TRY(d_order.alloc(nt));
-    HIP_TRY(d_ck.alloc(nc));
-    HIP_TRY(d_ck2.alloc(nc));
-    HIP_TRY(d_rank.alloc(nc));
-    HIP_TRY(d_rank2.alloc(nc));
-    HIP_TRY(d_heads.alloc(nc));
-    HIP_TRY(d_before.alloc(nc));
-    size_t b0 = 0, b1 = 0, b2 = 0;
-    HIP_TRY(gsdf_sort_pairs_u64(nullptr, &b0, d_keys, d_keys2, d_idx, d_order, nt, c->stream));
-    HIP_TRY(gsdf_sort_pairs_u64(nullptr, &b1, d_ck, d_ck2, d_rank, d_rank2, nc, c->stream));
-    HIP_TRY(gsdf_run_heads_scan(nullptr, &b2, d_ck2, d_heads, d_before, nc, c->stream));
-    HIP_TRY(d_tmp.alloc(std::max<size_t>(std::max(b0, b1), std::max<size_t>(b2, 8))));
-    HIP_TRY(hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream));
-    gsdf_launch_mesh_corners(c->stream, c->tab, c->n_slots, c->voxel_size, iso, d_mn, d_tab, d_tris, d_keys, d_ekeys, d_muw, c->counter,
-                             (long long)nt);
-    HIP_TRY(hipMemcpyAsync(&n2, c->counter, sizeof(n2), hipMemcpyDeviceToHost, c->stream));
-    /* the soup's order, then the weld: stable sort of (edge key, corner rank), run starts, their scan */
-    gsdf_launch_iota(c->stream, d_idx, nt);
-    b0 = d_tmp.bytes();
-    HIP_TRY(gsdf_sort_pairs_u64(d_tmp, &b0, d_keys, d_keys2, d_idx, d_order, nt, c->stream));
-    gsdf_launch_corner_keys(c->stream, d_ekeys, d_order, d_ck, d_rank, nt);
-    b1 = d_tmp.bytes();
-    HIP_TRY(gsdf_sort_pairs_u64(d_tmp, &b1, d_ck, d_ck2, d_rank, d_rank2, nc, c->stream));
-    b2 = d_tmp.bytes();
-    HIP_TRY(gsdf_run_heads_scan(d_tmp, &b2, d_ck2, d_heads, d_before, nc, c->stream));
-    uint32_t last[2] = { 0u, 0u };
-    HIP_TRY(hipMemcpyAsync(&last[0], d_before + (nc - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&last[1], d_heads + (nc - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (n2 != n) return fail(GSDF_ERR_HIP, "gsdf_extract_mesh_indexed: the map changed between the counting and the corner pass");
-    const size_t nv = (size_t)last[0] + last[1];
+    indexed_mesh_dev m;
+    if (int rc = indexed_mesh_count(c, iso, tri_table, "gsdf_extract_mesh_indexed", m)) return rc;
+    if (m.nt == 0) return GSDF_OK;
+    const size_t nv = m.nv, nt = m.nt, nc = m.nc;
     *n_vertices = (int64_t)nv; *n_faces = (int64_t)nt;
     if (max_vertices == 0 && max_faces == 0) return GSDF_OK;                    /* the sizing call */
     if ((int64_t)nv > max_vertices || (int64_t)nt > max_faces)
         return fail(GSDF_ERR_INVALID, "gsdf_extract_mesh_indexed: max_vertices or max_faces too small (n_vertices / n_faces hold the need)");
-    gsdf_dev<int32_t> d_faces;
-    gsdf_dev<float> d_v, d_n;
-    gsdf_dev<unsigned long long> d_vkeys;
-    gsdf_dev<uint32_t> d_vmuw;
-    HIP_TRY(d_faces.alloc(nc));
-    HIP_TRY(d_v.alloc(nv * 3));
-    HIP_TRY(d_vkeys.alloc(nv));
-    HIP_TRY(d_vmuw.alloc(nv));
-    if (normals_out) HIP_TRY(d_n.alloc(nv * 3));
-    gsdf_launch_weld(c->stream, d_ck2, d_rank2, d_heads, d_before, d_order, d_tris, d_muw, nc, d_faces, d_v, d_vkeys, d_vmuw);
-    if (normals_out) gsdf_launch_vertex_normals(c->stream, c->tab, d_mn, d_vkeys, d_vmuw, nv, d_n);
+    if (int rc = indexed_mesh_weld(c, normals_out != nullptr, m)) return rc;
+    HIP_TRY(hipMemcpyAsync(vertices_out, m.v, nv * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(faces_out, m.faces, nc * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (normals_out) HIP_TRY(hipMemcpyAsync(normals_out, m.n, nv * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return GSDF_OK;
+}
+
+/* The components of the welded mesh (steps at the head of gsdf_mesh_components.hip), shared by gsdf_mesh_components and
+ * gsdf_extract_mesh_indexed_filtered: labels, ids, and -- where asked for -- the tables.  Synchronises once, for the count. */
+namespace {
+struct mesh_components_dev {
+    gsdf_dev<uint32_t> parent, root, flags, before, box_bits;
+    gsdf_dev<int32_t> vcomp, fcomp, counts;
+    gsdf_dev<float> box;
+    gsdf_dev<void> tmp;
+    size_t n_comp = 0;
+};
+
+int mesh_components_label(gsdf_ctx* c, const indexed_mesh_dev& m, bool boxes, mesh_components_dev& cc) {
+    const size_t nv = m.nv, nt = m.nt;
+    HIP_TRY(cc.parent.alloc(nv));
+    HIP_TRY(cc.root.alloc(nv));
+    HIP_TRY(cc.flags.alloc(std::max(nv, nt)));                  /* reused for the keep flags of vertices, then of faces */
+    HIP_TRY(cc.before.alloc(nv));
+    HIP_TRY(cc.vcomp.alloc(nv));
+    HIP_TRY(cc.fcomp.alloc(nt));
+    size_t bytes = 0;
+    HIP_TRY(gsdf_scan_u32(nullptr, &bytes, cc.flags, cc.before, std::max(nv, nt), c->stream));
+    HIP_TRY(cc.tmp.alloc(std::max<size_t>(bytes, 8)));
+    gsdf_launch_cc_label(c->stream, m.faces, nt, nv, cc.parent, cc.root, cc.flags);
+    bytes = cc.tmp.bytes();
+    HIP_TRY(gsdf_scan_u32(cc.tmp, &bytes, cc.flags, cc.before, nv, c->stream));
+    uint32_t last[2] = { 0u, 0u };
+    HIP_TRY(hipMemcpyAsync(&last[0], cc.before + (nv - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&last[1], cc.flags + (nv - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(vertices_out, d_v, nv * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(faces_out, d_faces, nc * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (normals_out) HIP_TRY(hipMemcpyAsync(normals_out, d_n, nv * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    cc.n_comp = (size_t)last[0] + last[1];
+    HIP_TRY(cc.counts.alloc(cc.n_comp * 2));
+    if (boxes) { HIP_TRY(cc.box_bits.alloc(cc.n_comp * 6)); HIP_TRY(cc.box.alloc(cc.n_comp * 6)); }
+    gsdf_launch_cc_tables(c->stream, m.faces, m.v, cc.root, cc.before, nt, nv, cc.n_comp, cc.vcomp, cc.fcomp, cc.counts,
+                          boxes ? cc.box_bits.get() : nullptr, boxes ? cc.box.get() : nullptr);
+    HIP_TRY(hipGetLastError());
+    return GSDF_OK;
+}
+} // namespace
+
+int gsdf_mesh_components(gsdf_ctx* c, float iso, const int8_t tri_table[256 * 16], int32_t* vertex_comp, int32_t* face_comp,
+                         int64_t max_vertices, int64_t max_faces, int32_t* comp_counts, float* comp_bbox, int64_t max_components,
+                         int64_t* n_vertices, int64_t* n_faces, int64_t* n_components) {
+    GSDF_FLUSH(c);
+    if (!c || !n_vertices || !n_faces || !n_components) return fail(GSDF_ERR_INVALID, "null argument");
+    if (max_vertices < 0 || max_faces < 0 || max_components < 0) return fail(GSDF_ERR_INVALID, "gsdf_mesh_components: a negative maximum");
+    if (!tri_table) tri_table = GSDF_MC_TRI_TABLE;
+    HIP_TRY(hipSetDevice(c->device));
+    *n_vertices = 0; *n_faces = 0; *n_components = 0;
+    indexed_mesh_dev m;
+    if (int rc = indexed_mesh_count(c, iso, tri_table, "gsdf_mesh_components", m)) return rc;
+    if (m.nt == 0) return GSDF_OK;
+    if (int rc = indexed_mesh_weld(c, false, m)) return rc;
+    mesh_components_dev cc;
+    if (int rc = mesh_components_label(c, m, comp_bbox != nullptr, cc)) return rc;
+    const size_t nv = m.nv, nt = m.nt, ncomp = cc.n_comp;
+    *n_vertices = (int64_t)nv; *n_faces = (int64_t)nt; *n_components = (int64_t)ncomp;
+    if (max_vertices == 0 && max_faces == 0 && max_components == 0) {           /* the sizing call */
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return GSDF_OK;
+    }
+    if ((vertex_comp && (int64_t)nv > max_vertices) || (face_comp && (int64_t)nt > max_faces) ||
+        ((comp_counts || comp_bbox) && (int64_t)ncomp > max_components)) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return fail(GSDF_ERR_INVALID, "gsdf_mesh_components: max_vertices, max_faces or max_components too small (the counts hold the need)");
+    }
+    if (vertex_comp) HIP_TRY(hipMemcpyAsync(vertex_comp, cc.vcomp, nv * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (face_comp) HIP_TRY(hipMemcpyAsync(face_comp, cc.fcomp, nt * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (comp_counts) HIP_TRY(hipMemcpyAsync(comp_counts, cc.counts, ncomp * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (comp_bbox) HIP_TRY(hipMemcpyAsync(comp_bbox, cc.box, ncomp * 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return GSDF_OK;
+}
+
+int gsdf_extract_mesh_indexed_filtered(gsdf_ctx* c, float iso, const int8_t tri_table[256 * 16], int64_t min_faces, float* vertices_out,
+                                       float* normals_out, int32_t* faces_out, int64_t max_vertices, int64_t max_faces,
+                                       int64_t* n_vertices, int64_t* n_faces, int64_t* n_components, int64_t* n_kept) {
+    GSDF_FLUSH(c);
+    if (!c || !n_vertices || !n_faces || !n_components || !n_kept || (max_vertices > 0 && !vertices_out) || (max_faces > 0 && !faces_out))
+        return fail(GSDF_ERR_INVALID, "null argument");
+    if (min_faces < 1 && min_faces != GSDF_MESH_KEEP_LARGEST)
+        return fail(GSDF_ERR_INVALID, "gsdf_extract_mesh_indexed_filtered: min_faces must be >= 1 or GSDF_MESH_KEEP_LARGEST");
+    if (!tri_table) tri_table = GSDF_MC_TRI_TABLE;
+    HIP_TRY(hipSetDevice(c->device));
+    *n_vertices = 0; *n_faces = 0; *n_components = 0; *n_kept = 0;
+    indexed_mesh_dev m;
+    if (int rc = indexed_mesh_count(c, iso, tri_table, "gsdf_extract_mesh_indexed_filtered", m)) return rc;
+    if (m.nt == 0) return GSDF_OK;
+    const bool sizing = max_vertices == 0 && max_faces == 0;
+    if (int rc = indexed_mesh_weld(c, normals_out != nullptr && !sizing, m)) return rc;
+    mesh_components_dev cc;
+    if (int rc = mesh_components_label(c, m, false, cc)) return rc;
+    const size_t nv = m.nv, nt = m.nt;
+    /* the mask over the components, then per vertex and per face; the exclusive scans of the two are the new ids */
+    gsdf_dev<uint32_t> d_keep, d_kept, d_vbefore, d_fflags, d_fbefore;
+    HIP_TRY(d_keep.alloc(cc.n_comp));
+    HIP_TRY(d_kept.alloc(1));
+    HIP_TRY(d_vbefore.alloc(nv));
+    HIP_TRY(d_fflags.alloc(nt));
+    HIP_TRY(d_fbefore.alloc(nt));
+    uint32_t* d_vflags = cc.flags;                                              /* the root flags have been scanned: reuse */
+    gsdf_launch_cc_keep(c->stream, cc.counts, cc.n_comp, (long long)min_faces, d_keep, d_kept);
+    gsdf_launch_cc_keep_flags(c->stream, cc.vcomp, d_keep, nv, d_vflags);
+    gsdf_launch_cc_keep_flags(c->stream, cc.fcomp, d_keep, nt, d_fflags);
+    size_t bytes = cc.tmp.bytes();
+    HIP_TRY(gsdf_scan_u32(cc.tmp, &bytes, d_vflags, d_vbefore, nv, c->stream));
+    bytes = cc.tmp.bytes();
+    HIP_TRY(gsdf_scan_u32(cc.tmp, &bytes, d_fflags, d_fbefore, nt, c->stream));
+    uint32_t h[5] = { 0u, 0u, 0u, 0u, 0u };
+    HIP_TRY(hipMemcpyAsync(&h[0], d_kept, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&h[1], d_vbefore + (nv - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&h[2], d_vflags + (nv - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&h[3], d_fbefore + (nt - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&h[4], d_fflags + (nt - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const size_t kv = (size_t)h[1] + h[2], kf = (size_t)h[3] + h[4];
+    *n_vertices = (int64_t)kv; *n_faces = (int64_t)kf; *n_components = (int64_t)cc.n_comp; *n_kept = (int64_t)h[0];
+    if (sizing) return GSDF_OK;
+    if ((int64_t)kv > max_vertices || (int64_t)kf > max_faces)
+        return fail(GSDF_ERR_INVALID,
+                    "gsdf_extract_mesh_indexed_filtered: max_vertices or max_faces too small (n_vertices / n_faces hold the need)");
+    if (kf == 0) return GSDF_OK;
+    gsdf_dev<float> d_vo, d_no;
+    gsdf_dev<int32_t> d_fo;
+    HIP_TRY(d_vo.alloc(kv * 3));
+    if (normals_out) HIP_TRY(d_no.alloc(kv * 3));
+    HIP_TRY(d_fo.alloc(kf * 3));
+    gsdf_launch_cc_compact(c->stream, m.v, normals_out ? m.n.get() : nullptr, m.faces, d_vflags, d_vbefore, d_fflags, d_fbefore, nv, nt, d_vo,
+                           normals_out ? d_no.get() : nullptr, d_fo);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(vertices_out, d_vo, kv * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(faces_out, d_fo, kf * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (normals_out) HIP_TRY(hipMemcpyAsync(normals_out, d_no, kv * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return GSDF_OK;
 }

@@ -218,6 +218,24 @@ void gsdf_launch_weld(hipStream_t s, const unsigned long long* sorted, const uin
 void gsdf_launch_vertex_normals(hipStream_t s, gsdf_table tab, const int* mn_dev, const unsigned long long* vkeys, const uint32_t* vmuw,
                                 size_t n_vertices, float* normals);
 
+/* connected components of the indexed mesh (gsdf_mesh_components.hip).  label: parent[v] = v, the lock-free union over the faces,
+ * then root[v] and flags[v] = (root[v] == v); scan_u32: rocPRIM exclusive scan (tmp == nullptr: only *tmp_bytes is set); tables:
+ * vcomp[v] = before[root[v]], fcomp[f], counts (faces, vertices per component; zeroed here) and, with box_bits != nullptr, the
+ * bounding boxes (6 words of scratch and 6 floats per component); keep: the mask over the components for min_faces >= 1, or the
+ * largest (lowest id among equals) for min_faces < 0, and *n_kept; keep_flags: flags[i] = keep[comp[i]]; compact: the kept
+ * vertices and faces in their order, ids remapped through vbefore (nrm / n_out nullable together) */
+void gsdf_launch_cc_label(hipStream_t s, const int32_t* faces, size_t n_faces, size_t n_vertices, uint32_t* parent, uint32_t* root,
+                          uint32_t* flags);
+hipError_t gsdf_scan_u32(void* tmp, size_t* tmp_bytes, const uint32_t* in, uint32_t* out, size_t n, hipStream_t s);
+void gsdf_launch_cc_tables(hipStream_t s, const int32_t* faces, const float* vertices, const uint32_t* root, const uint32_t* before,
+                           size_t n_faces, size_t n_vertices, size_t n_comp, int32_t* vcomp, int32_t* fcomp, int32_t* counts,
+                           uint32_t* box_bits, float* box);
+void gsdf_launch_cc_keep(hipStream_t s, const int32_t* counts, size_t n_comp, long long min_faces, uint32_t* keep, uint32_t* n_kept);
+void gsdf_launch_cc_keep_flags(hipStream_t s, const int32_t* comp, const uint32_t* keep, size_t n, uint32_t* flags);
+void gsdf_launch_cc_compact(hipStream_t s, const float* v, const float* nrm, const int32_t* faces, const uint32_t* vflags,
+                            const uint32_t* vbefore, const uint32_t* fflags, const uint32_t* fbefore, size_t n_vertices, size_t n_faces,
+                            float* v_out, float* n_out, int32_t* f_out);
+
 /* dense block exchange (frame-sharded fusion): list of block keys; pack / unpack of 64 x 5 raw sums per listed block */
 void gsdf_launch_block_keys(hipStream_t s, gsdf_table tab, size_t n_blocks, unsigned long long* out_dev, unsigned long long* counter,
                             long long max_n);

@@ -138,6 +138,21 @@ bool MapGradPixelSdf::extract_pc(std::string filename) { return gsdf_exports::wr
 bool MapGradPixelSdf::save_sdf(std::string filename) { return gsdf_exports::write_sdf_txt(ctx_, voxel_size_, filename); }
 bool MapGradPixelSdf::extract_mesh(std::string filename) { return gsdf_exports::write_mesh_ply(ctx_, voxel_size_, filename, nullptr); }
 bool MapGradPixelSdf::extract_mesh_indexed(std::string filename) { return gsdf_exports::write_indexed_mesh_ply(ctx_, filename, nullptr, nullptr); }
+bool MapGradPixelSdf::extract_mesh_indexed(std::string filename, int64_t min_faces, long* n_components, long* n_kept, long* n_faces,
+                                           long* n_faces_all) {
+    return gsdf_exports::write_filtered_mesh_ply(ctx_, filename, min_faces, n_components, n_kept, n_faces, n_faces_all);
+}
+bool MapGradPixelSdf::mesh_components(MeshComponents& out) const {
+    int64_t nv = 0, nf = 0, nc = 0;
+    if (gsdf_mesh_components(ctx_, 0.f, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0, &nv, &nf, &nc) != GSDF_OK) return false;
+    out.vertex_comp.assign((size_t)nv, 0); out.face_comp.assign((size_t)nf, 0);
+    out.counts.assign((size_t)nc * 2, 0); out.bbox.assign((size_t)nc * 6, 0.f);
+    out.n_components = nc;
+    if (nf == 0) return true;
+    return gsdf_mesh_components(ctx_, 0.f, nullptr, out.vertex_comp.data(), out.face_comp.data(), nv, nf, out.counts.data(), out.bbox.data(), nc,
+                                &nv, &nf, &nc) == GSDF_OK;
+}
+bool MapGradPixelSdf::save_mesh_components(std::string filename) const { return gsdf_exports::write_mesh_components_txt(ctx_, filename, nullptr); }
 bool MapGradPixelSdf::gradient_analysis(const std::vector<float>& spheres4, const std::vector<float>& thresholds, std::vector<double>& stats) const {
     if (spheres4.empty() || spheres4.size() % 4 != 0 || thresholds.empty()) return false;
     stats.assign(4 * thresholds.size() * 5, 0.0);

@@ -59,6 +59,21 @@ public:
     /* the same surface as an indexed mesh with a gradient normal per vertex, binary PLY (gsdf_extract_mesh_indexed; not in the
      * reference).  MapPixelSdf inherits it: a base context stores the same gradient sums */
     bool extract_mesh_indexed(std::string filename);
+    /* ... without its small connected components (gsdf_extract_mesh_indexed_filtered): min_faces >= 1 keeps the components of at
+     * least that many faces, GSDF_MESH_KEEP_LARGEST the largest alone.  Nullable: components found / kept, faces written / of the
+     * whole mesh.  false when no face is kept or the file cannot be written */
+    bool extract_mesh_indexed(std::string filename, int64_t min_faces, long* n_components = nullptr, long* n_kept = nullptr,
+                              long* n_faces = nullptr, long* n_faces_all = nullptr);
+    /* the components of the indexed mesh (gsdf_mesh_components): an id per vertex and per face, per component faces / vertices
+     * and the box min x y z, max x y z.  false when the library refuses */
+    struct MeshComponents {
+        std::vector<int32_t> vertex_comp, face_comp, counts;             /* counts: 2 per component */
+        std::vector<float> bbox;                                         /* 6 per component */
+        int64_t n_components = 0;
+    };
+    bool mesh_components(MeshComponents& out) const;
+    /* ... its table written as text (gsdf_exports::write_mesh_components_txt) */
+    bool save_mesh_components(std::string filename) const;
     /* the gradient-accuracy table of a sphere scene (gsdf_gradient_stats; matlab/GradientAnalysisSpheres.m, phi_statistics.m):
      * spheres4 = rows cx cy cz R, thresholds ascending; stats = [4 estimators][thresholds][count, mean, median, rmse, p95].
      * false when the library refuses the arguments.  MapPixelSdf inherits it */

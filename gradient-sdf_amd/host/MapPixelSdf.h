@@ -24,7 +24,7 @@ public:
 
     bool extract_pc(std::string filename) override;                    /* MapPixelSdf.cpp:242-277 */
     bool save_sdf(std::string filename) override;                      /* MapPixelSdf.cpp:285-347 */
-    /* extract_mesh, extract_mesh_indexed and gradient_analysis: MapGradPixelSdf's (MapPixelSdf.cpp:192-240 runs the same marching
+    /* extract_mesh, extract_mesh_indexed (plain and filtered), mesh_components and gradient_analysis: MapGradPixelSdf's (MapPixelSdf.cpp:192-240 runs the same marching
      * cubes over the same dist values; the fusion stores the same gradient sums) */
 };
 

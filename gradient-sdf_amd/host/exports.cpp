@@ -138,6 +138,43 @@ bool write_indexed_mesh_ply(gsdf_ctx* ctx, const std::string& filename, long* n_
     return MarchingCubes::saveIndexedPly(filename, v, n, f);
 }
 
+bool write_filtered_mesh_ply(gsdf_ctx* ctx, const std::string& filename, int64_t min_faces, long* n_components, long* n_kept,
+                             long* n_faces, long* n_faces_all) {
+    int64_t nv = 0, nf = 0, nc = 0, nk = 0, nv_all = 0, nf_all = 0;
+    if (gsdf_extract_mesh_indexed(ctx, 0.f, nullptr, nullptr, nullptr, nullptr, 0, 0, &nv_all, &nf_all) != GSDF_OK) return false;
+    if (gsdf_extract_mesh_indexed_filtered(ctx, 0.f, nullptr, min_faces, nullptr, nullptr, nullptr, 0, 0, &nv, &nf, &nc, &nk) != GSDF_OK) return false;
+    if (n_components) *n_components = (long)nc;
+    if (n_kept) *n_kept = (long)nk;
+    if (n_faces) *n_faces = (long)nf;
+    if (n_faces_all) *n_faces_all = (long)nf_all;
+    if (nf <= 0) return false;
+    std::vector<float> v((size_t)nv * 3), n((size_t)nv * 3);
+    std::vector<int32_t> f((size_t)nf * 3);
+    if (gsdf_extract_mesh_indexed_filtered(ctx, 0.f, nullptr, min_faces, v.data(), n.data(), f.data(), nv, nf, &nv, &nf, &nc, &nk) != GSDF_OK)
+        return false;
+    return MarchingCubes::saveIndexedPly(filename, v, n, f);
+}
+
+bool write_mesh_components_txt(gsdf_ctx* ctx, const std::string& filename, long* n_components) {
+    int64_t nv = 0, nf = 0, nc = 0;
+    if (gsdf_mesh_components(ctx, 0.f, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0, &nv, &nf, &nc) != GSDF_OK) return false;
+    std::vector<int32_t> counts((size_t)nc * 2);
+    std::vector<float> box((size_t)nc * 6);
+    if (nc > 0 && gsdf_mesh_components(ctx, 0.f, nullptr, nullptr, nullptr, 0, 0, counts.data(), box.data(), nc, &nv, &nf, &nc) != GSDF_OK)
+        return false;
+    if (n_components) *n_components = (long)nc;
+    FILE* f = std::fopen(filename.c_str(), "w");
+    if (!f) return false;
+    std::fprintf(f, "# components of the indexed mesh (%lld vertices, %lld faces): id faces vertices minx miny minz maxx maxy maxz\n",
+                 (long long)nv, (long long)nf);
+    for (int64_t i = 0; i < nc; ++i) {
+        const float* b = &box[(size_t)i * 6];
+        std::fprintf(f, "%lld %d %d %.9g %.9g %.9g %.9g %.9g %.9g\n", (long long)i, counts[2 * i], counts[2 * i + 1], (double)b[0], (double)b[1],
+                     (double)b[2], (double)b[3], (double)b[4], (double)b[5]);
+    }
+    return std::fclose(f) == 0;
+}
+
 std::vector<float> gradient_ladder(float trunc_dist) {
     const long n = (long)std::floor((double)trunc_dist / 0.001 + 1e-3);
     std::vector<float> d;

@@ -22,6 +22,14 @@ bool write_mesh_ply(gsdf_ctx* ctx, float voxel_size, const std::string& filename
 /* the same surface as an indexed mesh with gradient normals (gsdf_extract_mesh_indexed; not in the reference), binary PLY
  * (MarchingCubes::saveIndexedPly); *n_vertices / *n_faces (nullable) = what was written.  false for an empty mesh, like write_mesh_ply */
 bool write_indexed_mesh_ply(gsdf_ctx* ctx, const std::string& filename, long* n_vertices, long* n_faces);
+/* that mesh without its small components (gsdf_extract_mesh_indexed_filtered: min_faces >= 1, or GSDF_MESH_KEEP_LARGEST), binary
+ * PLY; nullable: *n_components / *n_kept = components found / kept, *n_faces / *n_faces_all = faces written / of the whole mesh.
+ * false for a mesh that keeps no face */
+bool write_filtered_mesh_ply(gsdf_ctx* ctx, const std::string& filename, int64_t min_faces, long* n_components, long* n_kept,
+                             long* n_faces, long* n_faces_all);
+/* the component table of the indexed mesh (gsdf_mesh_components) as text: one row `id faces vertices minx miny minz maxx maxy maxz`
+ * per component behind a `#` line; *n_components (nullable) = rows written */
+bool write_mesh_components_txt(gsdf_ctx* ctx, const std::string& filename, long* n_components);
 /* the thresholds of matlab/GradientAnalysisSpheres.m:155, d = 0.001 : 0.001 : trunc_dist, as floats; the count forgives the
  * float rounding of trunc_dist by a thousandth of a step (5 voxels of 0.02 m are 0.099999994: 100 thresholds) */
 std::vector<float> gradient_ladder(float trunc_dist);

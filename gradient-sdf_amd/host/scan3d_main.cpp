@@ -19,6 +19,10 @@
  *   --transport shm   the exchange through host shared memory instead of RCCL: N ranks on ONE device (test boxes).
  *   --mesh-indexed    additionally write <results>mesh_indexed.ply: the same surface with one vertex per crossed grid edge,
  *                     faces as indices and gradient normals, binary PLY (gsdf_extract_mesh_indexed);
+ *   --mesh-min-faces <N|largest>
+ *                     additionally write <results>mesh_indexed_clean.ply: the indexed mesh without its connected components of
+ *                     fewer than N faces, or its largest component alone (gsdf_extract_mesh_indexed_filtered), and print
+ *                     `Mesh components: C, kept K, faces F of F0`; independent of --mesh-indexed;
  *   --gradient-analysis <spheres.txt>
  *                     after the other exports write <results>gradient_sdf_gradient_stats.txt: the angle between the stored /
  *                     central / forward / backward gradient and the analytic one of the sphere scene in the file (rows
@@ -61,6 +65,7 @@ struct Options {
     int max_capacity_log2 = 28;          /* the table doubles by itself up to this (the reference's map has no capacity) */
     int gpus = 1, rank = -1, decode_threads = 0;
     std::string transport = "rccl", rendezvous, gradient_spheres;
+    long long mesh_min_faces = 0;        /* 0: no filtered mesh; GSDF_MESH_KEEP_LARGEST: --mesh-min-faces largest */
 };
 
 bool parse(int argc, char** argv, Options& o) {
@@ -74,7 +79,7 @@ bool parse(int argc, char** argv, Options& o) {
         if (a == "-h" || a == "--help") {
             std::cout << "Hash Table-Based 3D Scanning (MI355X)\n  --input --results --pose-file --first --last --scan-type"
                          " --data-type --voxel-size --trunc --save-sdf --width --height --hash-capacity --hash-max-capacity --device"
-                         " --sync --decode-threads --gpus --transport rccl|shm --mesh-indexed --gradient-analysis <spheres.txt>\n"
+                         " --sync --decode-threads --gpus --transport rccl|shm --mesh-indexed --mesh-min-faces <N|largest> --gradient-analysis <spheres.txt>\n"
                          "  --scan-type grad-sdf|base-sdf (base-sdf: one GPU only, --gpus 1)\n";
             std::exit(0);
         }
@@ -99,6 +104,10 @@ bool parse(int argc, char** argv, Options& o) {
         else if (a == "--transport") o.transport = v;
         else if (a == "--decode-threads") o.decode_threads = std::stoi(v);
         else if (a == "--gradient-analysis") o.gradient_spheres = v;
+        else if (a == "--mesh-min-faces") {
+            o.mesh_min_faces = v == "largest" ? (long long)GSDF_MESH_KEEP_LARGEST : std::atoll(v.c_str());
+            if (v != "largest" && o.mesh_min_faces < 1) { std::cerr << "--mesh-min-faces takes a count >= 1 or `largest`" << std::endl; return false; }
+        }
         else { std::cerr << "unknown option " << a << std::endl; return false; }
     }
     return true;
@@ -455,6 +464,15 @@ int run(int, char**, Options& opt) {
         filename = opt.output + "mesh_indexed.ply";
         if (!tSDF->extract_mesh_indexed(filename)) std::cerr << "Could not save indexed mesh to " << filename << "!" << std::endl;
         T.toc("Save indexed mesh to disk");
+    }
+    if (opt.mesh_min_faces != 0) {
+        T.tic();
+        filename = opt.output + "mesh_indexed_clean.ply";
+        long n_comp = 0, n_kept = 0, n_faces = 0, n_all = 0;
+        if (!tSDF->extract_mesh_indexed(filename, opt.mesh_min_faces, &n_comp, &n_kept, &n_faces, &n_all))
+            std::cerr << "Could not save the filtered indexed mesh to " << filename << "!" << std::endl;
+        std::cout << "Mesh components: " << n_comp << ", kept " << n_kept << ", faces " << n_faces << " of " << n_all << std::endl;
+        T.toc("Save filtered indexed mesh to disk");
     }
     T.tic();
     filename = opt.output + prefix + "_cloud_final.ply";

@@ -489,6 +489,44 @@ int gsdf_extract_mesh_indexed(gsdf_ctx* c, float iso, const int8_t tri_table[256
                               int32_t* faces_out /* 3 per face */, int64_t max_vertices, int64_t max_faces,
                               int64_t* n_vertices, int64_t* n_faces);
 
+/* CONNECTED COMPONENTS of the indexed mesh, and the mesh without its small fragments.  Not in the reference (a triangle soup has
+ * no neighbours to find).  Noise at depth edges leaves isolated voxels in a fused map, and marching cubes turns them into islands
+ * of a face or two beside the scanned surface.
+ *  - Mesh and graph: the mesh is that of gsdf_extract_mesh_indexed(iso, tri_table) -- the same vertices, ids, faces and order.
+ *    Two vertices are adjacent iff some face names both; a component is a connected component of that graph.  Faces that share
+ *    only a vertex are therefore connected.  Every vertex lies in a face, so every component has at least one face.
+ *  - Component ids: 0 .. C-1 in ascending order of the component's smallest vertex id (component 0 holds vertex 0).  A function
+ *    of the mesh alone, not of any order of execution.
+ * gsdf_mesh_components: vertex_comp[v] the id per vertex; face_comp[f] the id per face (the component of its vertices);
+ * comp_counts 2 int32 per component: faces, vertices; comp_bbox 6 floats per component: min x, y, z then max x, y, z of its vertex
+ * positions (the floats of vertices_out; where a component holds both zeros, either sign of zero may be reported).  Each of the
+ * four arrays may be NULL.  max_vertices belongs to vertex_comp, max_faces to face_comp, max_components to comp_counts and
+ * comp_bbox.  Conventions of gsdf_extract_mesh_indexed: all three maxima 0 sizes the outputs; the three counts are always
+ * reported; if a maximum that belongs to a non-NULL array is too small nothing is written to any array and the call returns
+ * GSDF_ERR_INVALID; an empty map gives 0 / 0 / 0 and GSDF_OK; the table is only read; base contexts are accepted.
+ * Deterministic: the same map gives the same bytes, run to run and across gsdf_grow. */
+int gsdf_mesh_components(gsdf_ctx* c, float iso, const int8_t tri_table[256 * 16],
+                         int32_t* vertex_comp /* 1 per vertex, nullable */, int32_t* face_comp /* 1 per face, nullable */,
+                         int64_t max_vertices, int64_t max_faces,
+                         int32_t* comp_counts /* 2 per component, nullable */, float* comp_bbox /* 6 per component, nullable */,
+                         int64_t max_components, int64_t* n_vertices, int64_t* n_faces, int64_t* n_components);
+
+/* gsdf_extract_mesh_indexed restricted to the components that are kept:
+ *  - min_faces >= 1 keeps the components with at least that many faces; min_faces == GSDF_MESH_KEEP_LARGEST keeps the one
+ *    component with the most faces, among equals the one with the lowest id; any other value is GSDF_ERR_INVALID.
+ *  - Output vertices are the kept vertices in ascending original id, position and normal bytes unchanged; a vertex's new id is
+ *    its rank among the kept.  Output faces are the kept faces in their original order with the ids remapped.
+ *  - *n_vertices and *n_faces are the FILTERED counts, which is also what the sizing call (both maxima 0) reports;
+ *    *n_components counts all components, *n_kept the kept ones.  All four are always reported.
+ *  - min_faces = 1 returns the bytes of gsdf_extract_mesh_indexed.  A threshold above every component gives 0 / 0 and GSDF_OK.
+ * Otherwise the conventions of gsdf_extract_mesh_indexed (normals_out nullable; a maximum that is too small: nothing is written,
+ * GSDF_ERR_INVALID).  Deterministic in the same sense. */
+#define GSDF_MESH_KEEP_LARGEST (-1)
+int gsdf_extract_mesh_indexed_filtered(gsdf_ctx* c, float iso, const int8_t tri_table[256 * 16], int64_t min_faces,
+                                       float* vertices_out /* 3 per vertex */, float* normals_out /* 3 per vertex, nullable */,
+                                       int32_t* faces_out /* 3 per face */, int64_t max_vertices, int64_t max_faces,
+                                       int64_t* n_vertices, int64_t* n_faces, int64_t* n_components, int64_t* n_kept);
+
 /* GRADIENT ACCURACY on a sphere scene: the angle between a voxel's gradient and the analytic one, for the gradient the map
  * STORES and for finite differences of the stored distances, and its statistics over the voxels near the surface -- the paper's
  * central measurement (matlab/GradientAnalysisSpheres.m, matlab/phi_statistics.m), on the map in HBM instead of save_sdf's text
