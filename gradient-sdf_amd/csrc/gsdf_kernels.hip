@@ -108,6 +108,77 @@ __device__ __forceinline__ void wave_sum_to_lane63(float (&v)[N]) {
 }
 #undef GSDF_DPP_STAGE
 
+/* The same sums by folding: the N <= 32 values are padded to 32, and at each stage the two halves of a lane group (pair, quad,
+ * octet, row, row pair, wave) exchange half of their values -- the lower lanes keep w[i], the upper ones w[i + half], each adds
+ * what its partner sends -- so a lane holds 16, 8, 4, 2, 1, 1 partial sums where wave_sum_to_lane63 carries all N through every
+ * stage: ~100 instructions for the tracker's 29 sums against 174, and the totals end in 32 different lanes (ONE LDS write).
+ * Returns the total of value bitrev5(lane & 31), in both halves of the wave.
+ * The additions are those of wave_sum_to_lane63, bit for bit: adjacent lanes, then adjacent pairs, quads, octets (the balanced
+ * tree row_shr:1,2,4,8 builds in lane 15 of a row), then row 0 + row 1 and row 2 + row 3, then those two; the lower lanes'
+ * partial sum is the first operand except in the lanes that keep the lower half in stages 1-4 (DPP permutes the first operand
+ * only; float addition is commutative).  tests/track_reduce_model.py states both trees lane by lane.
+ * Stages 1, 2: a lane selects what it sends and what it keeps (v_cndmask on a lane mask), then adds its partner's
+ * (quad_perm) to its own -- three instructions per pair of values, four pairs per block so that the DPP add reads its operand 7
+ * instructions after the select wrote it.  Stages 3, 4: the write mask of DPP works on banks of 4 lanes -- the lower banks add
+ * the upper banks' w[i] to theirs, the upper banks write their sum of w[i + half] over it: two instructions.  Stages 5, 6:
+ * v_permlane16_swap / v_permlane32_swap (gfx950) put the two rows / halves of one value side by side in two registers.
+ * Hazards kept by construction, as above: a VGPR written by a VALU instruction is not read by a DPP or permlane-swap
+ * instruction within the next two wait states -- every block that reads its inputs that way starts with s_nop 1. */
+#define GSDF_FOLD_SELECT(PERM)                                                                                     \
+    asm volatile("v_cndmask_b32_e64 %4, %8, %0, %12\n\tv_cndmask_b32_e64 %5, %9, %1, %12\n\t"                      \
+                 "v_cndmask_b32_e64 %6, %10, %2, %12\n\tv_cndmask_b32_e64 %7, %11, %3, %12\n\t"                    \
+                 "v_cndmask_b32_e64 %0, %0, %8, %12\n\tv_cndmask_b32_e64 %1, %1, %9, %12\n\t"                      \
+                 "v_cndmask_b32_e64 %2, %2, %10, %12\n\tv_cndmask_b32_e64 %3, %3, %11, %12\n\t"                    \
+                 "v_add_f32_dpp %0, %4, %0 " PERM " row_mask:0xf bank_mask:0xf\n\t"                                \
+                 "v_add_f32_dpp %1, %5, %1 " PERM " row_mask:0xf bank_mask:0xf\n\t"                                \
+                 "v_add_f32_dpp %2, %6, %2 " PERM " row_mask:0xf bank_mask:0xf\n\t"                                \
+                 "v_add_f32_dpp %3, %7, %3 " PERM " row_mask:0xf bank_mask:0xf"                                    \
+                 : "+v"(w[i]), "+v"(w[i + 1]), "+v"(w[i + 2]), "+v"(w[i + 3]), "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3) \
+                 : "v"(w[i + H]), "v"(w[i + H + 1]), "v"(w[i + H + 2]), "v"(w[i + H + 3]), "s"(upper))
+template <int N>
+__device__ __forceinline__ float wave_sum_fold(const float (&v)[N]) {
+    static_assert(N <= 32, "one value per lane of a half wave");
+    float w[32], t0, t1, t2, t3;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) w[i] = i < N ? v[i] : 0.f;
+    {   /* stage 1: lanes 2k, 2k + 1 */
+        constexpr int H = 16;
+        const unsigned long long upper = 0xAAAAAAAAAAAAAAAAull;
+#pragma unroll
+        for (int i = 0; i < H; i += 4) GSDF_FOLD_SELECT("quad_perm:[1,0,3,2]");
+    }
+    {   /* stage 2: lanes 4k .. 4k + 1, 4k + 2 .. 4k + 3 */
+        constexpr int H = 8;
+        const unsigned long long upper = 0xCCCCCCCCCCCCCCCCull;
+#pragma unroll
+        for (int i = 0; i < H; i += 4) GSDF_FOLD_SELECT("quad_perm:[2,3,0,1]");
+    }
+    /* stage 3: banks 0, 2 (lanes 0-3, 8-11 of a row) keep w[0..3], banks 1, 3 keep w[4..7] */
+    asm volatile("s_nop 1\n\t"
+                 "v_add_f32_dpp %0, %0, %0 row_shl:4 row_mask:0xf bank_mask:0x5\n\tv_add_f32_dpp %1, %1, %1 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+                 "v_add_f32_dpp %2, %2, %2 row_shl:4 row_mask:0xf bank_mask:0x5\n\tv_add_f32_dpp %3, %3, %3 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+                 "v_add_f32_dpp %0, %4, %4 row_shr:4 row_mask:0xf bank_mask:0xa\n\tv_add_f32_dpp %1, %5, %5 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
+                 "v_add_f32_dpp %2, %6, %6 row_shr:4 row_mask:0xf bank_mask:0xa\n\tv_add_f32_dpp %3, %7, %7 row_shr:4 row_mask:0xf bank_mask:0xa"
+                 : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]) : "v"(w[4]), "v"(w[5]), "v"(w[6]), "v"(w[7]));
+    /* stage 4: banks 0, 1 keep w[0..1], banks 2, 3 keep w[2..3]; stage 5: rows 0, 2 keep w[0], rows 1, 3 w[1]; stage 6: both halves
+     * end with (row 0 + row 1) + (row 2 + row 3) */
+    asm volatile("s_nop 1\n\t"
+                 "v_add_f32_dpp %0, %0, %0 row_shl:8 row_mask:0xf bank_mask:0x3\n\tv_add_f32_dpp %1, %1, %1 row_shl:8 row_mask:0xf bank_mask:0x3\n\t"
+                 "v_add_f32_dpp %0, %2, %2 row_shr:8 row_mask:0xf bank_mask:0xc\n\tv_add_f32_dpp %1, %3, %3 row_shr:8 row_mask:0xf bank_mask:0xc\n\t"
+                 "s_nop 1\n\t"
+                 "v_permlane16_swap_b32 %0, %1\n\t"        /* w0 = value a's row 0, b's row 0, a's row 2, b's row 2; w1 = the rows 1 and 3 */
+                 "s_nop 1\n\t"
+                 "v_add_f32 %0, %0, %1\n\t"
+                 "v_mov_b32 %1, %0\n\t"
+                 "s_nop 1\n\t"
+                 "v_permlane32_swap_b32 %0, %1\n\t"        /* w0 = the lower half's sums in both halves, w1 = the upper half's */
+                 "s_nop 1\n\t"
+                 "v_add_f32 %0, %0, %1"
+                 : "+v"(w[0]), "+v"(w[1]) : "v"(w[2]), "v"(w[3]));
+    return w[0];
+}
+#undef GSDF_FOLD_SELECT
+
 __device__ __forceinline__ int reflect101(int i, int n) {      /* cv::BORDER_REFLECT_101 */
     if (n == 1) return 0;
     while (i < 0 || i >= n) {
@@ -2135,10 +2206,16 @@ __global__ __launch_bounds__(GSDF_TRACK_BLOCK, BASE ? 2 : 4) void k_track_pass(g
     }
     if (trk_tr && threadIdx.x == 0) trk_tr[2] = wall_clock64();                         /* wave 0: gather done */
     /* every wave reduces its sums as soon as its own gather is done (wsum is used here only): ONE barrier per pass tail */
-    wave_sum_to_lane63(acc);
-    if (lane == 63) {
+    if (GSDF_EXPERIMENT(tp.debug, 8)) {                                                 /* test build: the reduction of rounds 1-6, for the A/B */
+        wave_sum_to_lane63(acc);
+        if (lane == 63) {
 #pragma unroll
-        for (int i = 0; i < GSDF_TRACK_NSUM; ++i) wsum[wave][i] = acc[i];
+            for (int i = 0; i < GSDF_TRACK_NSUM; ++i) wsum[wave][i] = acc[i];
+        }
+    } else {
+        /* wave_sum_fold: lane l < 32 holds the total of value bitrev5(l) -- the padding (29..31) included: zeros nobody reads */
+        const float total = wave_sum_fold(acc);
+        if (lane < 32) wsum[wave][__builtin_bitreverse32((uint32_t)lane) >> 27] = total;
     }
     if (trk_tr && threadIdx.x == 0) trk_tr[6] = wall_clock64();                         /* wave 0: its sums are in LDS */
     __syncthreads();
@@ -2163,7 +2240,8 @@ void gsdf_launch_track_pass(hipStream_t s, const gsdf_frame_geom& g, const float
     gsdf_track_params tp = tp_in;
     /* one chunk of TRK_CHUNK pixels per workgroup while the grid allows it (640 x 480: 240 workgroups), more by looping */
     {                                   /* ... and then the same number of chunks for every workgroup (1280 x 960: 480 x 2, not 512 x 1.9) */
-        const int chunks = std::max(1, (g.W * g.H + TRK_CHUNK - 1) / TRK_CHUNK), cap = std::max(1, n_blocks);
+        /* (test build, tracker debug bit 32: at most 4 workgroups, so that a small frame takes the loop over batches) */
+        const int chunks = std::max(1, (g.W * g.H + TRK_CHUNK - 1) / TRK_CHUNK), cap = std::max(1, GSDF_EXPERIMENT(tp.debug, 32) ? std::min(n_blocks, 4) : n_blocks);
         const int per = (chunks + cap - 1) / cap;
         n_blocks = (chunks + per - 1) / per;
     }
