@@ -26,6 +26,11 @@
 #define GSDF_EXPERIMENT(flags, mask) (false)
 #define GSDF_TRACE(a, tr, col) do { } while (0)
 #endif
+/* ... and the launch's last workgroup has a row of its own, behind the rows of the fusion and normals workgroups and below the
+ * tracker's (2048 ...): ticket answered, list length known, adds issued, bookkeeping stored, everything drained, then the list's
+ * length and the workgroup's index.  A workgroup's own row: 0 start, 1-12 phases, 13 ticket answered, 14 hardware id, 15 tile |
+ * bands << 32 | list entries of the tile's flush << 36 */
+#define GSDF_TRACE_LAST_ROW 2047
 #include "gsdf_math.h"
 
 #include <hip/hip_runtime.h>
@@ -647,6 +652,7 @@ __device__ __forceinline__ void hbm_accumulate(const gsdf_table& T, unsigned lon
 __device__ __forceinline__ void defer_append(const fuse_args& a, gsdf_payload* p, float w, float s, float gx, float gy,
                                              float gz) {
     const unsigned int i = atomicAdd(a.deferred_count, 1u);
+    if (GSDF_EXPERIMENT(a.debug, 64)) atomicAdd(&a.st->dbg[6], 1ull);     /* (trace) entries appended one by one from the walk */
     if (i >= a.deferred_cap) { atomicOr(&a.st->status, GSDF_STATUS_TABLE_FULL); return; }
     gsdf_deferred d;
     d.p = p; d.w = w; d.s = s; d.gx = gx; d.gy = gy; d.gz = gz; d.pad = 0u;
@@ -668,17 +674,32 @@ __device__ __forceinline__ void fuse_lds_clear(fuse_lds<LCAP>& L, int tid) {
     for (int i = tid; i < 3 * FUSE_LCAP / 2; i += FUSE_THREADS) a4[i] = gsdf_u32x4{ 0u, 0u, 0u, 0u };
 }
 
-/* per-frame log row of the Scan3D loop: pose7, converged, passes, hits of the last pass (main_scan_3d.cpp:268-280) */
-__device__ __forceinline__ void fuse_log_row(const fuse_args& a) {
-    if (!a.log_rows) return;
-    gsdf_dev_state* st = a.st;
-    const long long r = st->log_rows;
+/* per-frame log row of the Scan3D loop: pose7, converged, passes, hits of the last pass (main_scan_3d.cpp:268-280).
+ * Written by ONE thread at the FRONT of the tracked launch that sees optimize() ended -- the first lane of workgroup 0, from the
+ * head's result -- whether the launch then fuses or not.  It takes row `r` (st->log_rows, which the caller requested together with
+ * whatever else it reads) and the row's values in registers: the row may alias `st` for all the compiler knows, and a row written
+ * from memory is ten loads and stores strictly one after another (where the launch's last workgroup did that behind the last tile,
+ * the whole chip waited for it). */
+__device__ __forceinline__ void fuse_log_row(const fuse_args& a, long long r, const float (&pose)[7], int converged, int passes, float hits) {
     if (r < a.max_rows) {
         float* o = a.log_rows + 10 * r;
-        for (int i = 0; i < 7; ++i) o[i] = st->pose7[i];
-        o[7] = (float)st->converged; o[8] = (float)st->passes; o[9] = st->last_hits;
+#pragma unroll
+        for (int i = 0; i < 7; ++i) o[i] = pose[i];
+        o[7] = (float)converged; o[8] = (float)passes; o[9] = hits;
     }
-    st->log_rows = r + 1;
+    a.st->log_rows = r + 1;
+}
+/* the same from the state earlier kernels left in `st` (launches without the head): every load is issued before the first store */
+__device__ __forceinline__ void fuse_log_row_from_state(const fuse_args& a) {
+    if (!a.log_rows) return;
+    const gsdf_dev_state* st = a.st;
+    const long long r = st->log_rows;
+    float pose[7];
+#pragma unroll
+    for (int i = 0; i < 7; ++i) pose[i] = st->pose7[i];
+    const int converged = st->converged, passes = st->passes;
+    const float hits = st->last_hits;
+    fuse_log_row(a, r, pose, converged, passes, hits);
 }
 
 /* ------------------------------------------------------------------------------------------------
@@ -898,6 +919,9 @@ __device__ __forceinline__ void fuse_head(const fuse_args& a, int tid, bool solv
     const int hlane = tid & 63;
     int hpasses = 0;
     bool have = false;
+    /* the solver also writes the frame's log row (behind the chunks): its index is requested here, in front of the group sums */
+    const long long log_r = solver && a.log_rows ? a.st->log_rows : 0ll;
+    float hhits = 0.f;
     if (!solver) {
         /* the three chunks, one per lane 0..2, until all carry this launch's tag (for workgroups of the later dispatch rounds
          * they are there at the first look) */
@@ -936,6 +960,7 @@ __device__ __forceinline__ void fuse_head(const fuse_args& a, int tid, bool solv
     if (ended_before) {
         gsdf_dev_state* st = a.st;
         hdone = st->done; hconv = st->converged; hpasses = st->passes;
+        hhits = st->last_hits;
 #pragma unroll
         for (int i = 0; i < 7; ++i) pose[i] = st->pose7[i];
     } else {
@@ -950,6 +975,7 @@ __device__ __forceinline__ void fuse_head(const fuse_args& a, int tid, bool solv
                          GSDF_EXPERIMENT(a.hd.debug, 4), pose, &hdone, &hconv);
         /* published for the later launches and the host ... */
         if (solver && hlane == 0) trk_head_publish(a.st, a.hd.k, pose, hdone, hconv, hpasses, tot[28], a.hd.progress, a.hd.serial);
+        hhits = tot[28];
     }
     if (solver && hlane == 0) {
         /* ... and for every other wave of THIS launch: the tagged chunks (also when optimize() had ended before the launch) */
@@ -959,8 +985,13 @@ __device__ __forceinline__ void fuse_head(const fuse_args& a, int tid, bool solv
         unsigned int* q = a.st->fh;
         asm volatile("global_store_dwordx4 %0, %1, off sc1\n\tglobal_store_dwordx4 %0, %2, off offset:16 sc1\n\t"
                      "global_store_dwordx4 %0, %3, off offset:32 sc1" :: "v"(q), "v"(c0), "v"(c1), "v"(c2) : "memory");
-        /* the plain stores above are read by the launch's LAST workgroup (frame log), possibly on another XCD */
+        /* (the published state leaves this XCD's L2 now and not at the kernel's end: kept from when the launch's last workgroup
+         * read it for the frame log) */
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        /* The frame's log row, from the registers that hold the head's result: this launch has seen optimize() ended, so the row
+         * is its to write, whether it fuses (converged) or not.  Behind the chunks, so that no other wave waits for it; a wave that
+         * performed the head itself because its wait expired is not the solver and writes nothing. */
+        if (hdone && a.log_rows) fuse_log_row(a, log_r, pose, hconv, hpasses, hhits);
     }
 }
 
@@ -1000,8 +1031,14 @@ void k_fuse(fuse_args a) {
             if (!(gd && gc)) return;
             if (t == 0 && tid == 0) a.st->nrm_token = a.nrm_token;
         }
+        unsigned long long* ntr = nullptr;                 /* trace row of a normals workgroup: start, end (column 13), no tile */
+        if (GSDF_EXPERIMENT(a.debug, 64) && blockIdx.x < GSDF_TRACE_LAST_ROW) {
+            ntr = reinterpret_cast<unsigned long long*>(a.st->dbg[23]) + 16 * (size_t)blockIdx.x;
+            if (tid == 0) { ntr[0] = wall_clock64(); ntr[15] = 0xFFFFFFFFull; }
+        }
         normals_tile<FUSE_THREADS>(*reinterpret_cast<nrm_lds*>(&L), t % a.nrm_ntx, t / a.nrm_ntx, a.g.W, a.g.H, a.nrm_r, a.nc, a.nrm_depth, a.nrm_x,
                      a.nrm_y, a.nrm_z, gsdf_tile_stats{ a.nrm_stats, (a.g.W + 15) / 16, a.g.zmin, a.g.zmax });
+        if (GSDF_EXPERIMENT(a.debug, 64) && ntr) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); GSDF_TRACE(a, ntr, 13); }
         return;
     }
     }
@@ -1032,10 +1069,11 @@ void k_fuse(fuse_args a) {
         for (int i = 0; i < 3; ++i) t[i] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(pose[i])));
     }
     if (a.use_dev_pose) {
-        if (!(done && conv)) {
-            if (done && blockIdx.x == 0 && tid == 0) fuse_log_row(a);
-            return;
+        /* (with the head in the launch its solver lane has written the row: fuse_head) */
+        if constexpr (!HEAD) {
+            if (done && blockIdx.x == 0 && tid == 0) fuse_log_row_from_state(a);
         }
+        if (!(done && conv)) return;
     } else {
 #pragma unroll
         for (int i = 0; i < 9; ++i) R[i] = a.pose.R[i];
@@ -1209,6 +1247,7 @@ void k_fuse(fuse_args a) {
     range_ok = __builtin_amdgcn_readfirstlane(L.dec[5]) != 0;
     unsigned int n_upd_w = 0u, n_val_w = 0u;                          /* wave-uniform counters */
     unsigned int dbg_go = 0u, dbg_full = 0u, dbg_lost = 0u;
+    unsigned int tr_list = 0u;                                        /* (trace) entries this tile handed over as a list: near tile or expired wait */
     unsigned long long T1 = GSDF_EXPERIMENT(a.debug, 128) ? wall_clock64() : 0ull;
     GSDF_TRACE(a, tr, 1);                                             /* prologue done */
     if (GSDF_EXPERIMENT(a.debug, 128) && tid == 0) atomicAdd(&a.st->dbg[4], T1 - T0);
@@ -1597,6 +1636,7 @@ void k_fuse(fuse_args a) {
             __syncthreads();
             if (L.n_defer) {
                 if (tid == 0) { L.defer_base = atomicAdd(a.deferred_count, L.n_defer); L.any_defer = 1u; }   /* one global atomic per workgroup */
+                if (GSDF_EXPERIMENT(a.debug, 64)) tr_list += L.n_defer;
                 __syncthreads();
                 if (tid == 0) L.n_defer = 0u;
                 __syncthreads();
@@ -1629,7 +1669,9 @@ void k_fuse(fuse_args a) {
     }
     }   /* pass */
     GSDF_TRACE(a, tr, 10);                                            /* all bands done */
-    if (GSDF_EXPERIMENT(a.debug, 64) && tid == 0) tr[13] = (unsigned long long)n_pass;
+    /* (the tile word's unused half: the number of bands, and how many list entries of the tile came through the flush) */
+    if (GSDF_EXPERIMENT(a.debug, 64) && tid == 0)
+        tr[15] = (unsigned long long)tile_id | ((unsigned long long)n_pass << 32) | ((unsigned long long)(tr_list < 0xFFFFFu ? tr_list : 0xFFFFFu) << 36);
     /* per-workgroup counters (plain stores into this workgroup's own row: no hot atomics) */
     if (lane == 0) { L.cnt[0][wave] = n_upd_w; L.cnt[1][wave] = n_val_w; }
     /* every wave drains what it stored -- deferred-list entries among it -- before the barrier behind which thread 0 releases
@@ -1661,12 +1703,34 @@ void k_fuse(fuse_args a) {
         }
         L.is_last = atomicAdd(a.ticket, 1u) + 1u == (NEXT_NORMALS ? (unsigned int)a.n_tiles : gridDim.x) ? 1u : 0u;
         if (L.is_last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        GSDF_TRACE(a, tr, 13);                                        /* the ticket is answered: end of the workgroup's life */
     }
     __syncthreads();
     if (!L.is_last) return;
+    unsigned long long* ltr = nullptr;                                /* (trace) the last workgroup's own row */
+    if (GSDF_EXPERIMENT(a.debug, 64)) {
+        ltr = reinterpret_cast<unsigned long long*>(st_in->dbg[23]) + 16 * (size_t)GSDF_TRACE_LAST_ROW;
+        GSDF_TRACE(a, ltr, 0);
+    }
+    /* Behind the acquire, everything the rest of the kernel reads is requested together -- the three words of the bookkeeping by
+     * thread 0, then the list's length by every thread (in this order: the length is the first to be waited for, and the wait
+     * then covers the others) -- where they used to be four round trips of one thread, one after another, with the rest of the
+     * chip idle. */
+    unsigned long long n_deferred_was = 0ull;
+    unsigned int far_tiles = 0u;
+    long long frames = 0ll;
+    if (tid == 0) {
+        n_deferred_was = a.st->n_deferred;
+        far_tiles = __hip_atomic_load(&a.st->far_tiles, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        /* Sdf::counter_ as the NEXT update() will see it (this launch's increment included: tile (0, 0) arrived before this
+         * workgroup read the ticket).  The normals stage used to take this snapshot; in GT-pose mode it now runs on its own
+         * stream beside this kernel and must not touch state the fusion uses. */
+        frames = __hip_atomic_load(&a.st->frames, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     unsigned int n = __hip_atomic_load(a.deferred_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     n = n < a.deferred_cap ? n : a.deferred_cap;
     const bool mine = !(a.resolve_follows && n > FUSE_RESOLVE_INLINE);
+    if (GSDF_EXPERIMENT(a.debug, 64) && tid == 0) { ltr[1] = wall_clock64(); ltr[5] = n; ltr[6] = blockIdx.x; }
     if (mine)
         for (unsigned int i = tid; i < n; i += FUSE_THREADS) {
             const gsdf_deferred d = a.deferred[i];
@@ -1676,22 +1740,25 @@ void k_fuse(fuse_args a) {
             unsafeAtomicAdd(&d.p->gy, d.gy);
             unsafeAtomicAdd(&d.p->gz, d.gz);
         }
+    GSDF_TRACE(a, ltr, 2);                                            /* thread 0 has issued its adds */
     if (tid == 0) {
-        if (mine) { a.st->n_deferred += n; __hip_atomic_store(a.deferred_count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+        if (mine) { a.st->n_deferred = n_deferred_was + n; __hip_atomic_store(a.deferred_count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
         a.st->last_deferred = n;
         /* the host decides by it, without waiting, whether the next launches get a k_fuse_resolve behind them */
         if (a.host_note) {
             __hip_atomic_store(a.host_note, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(a.host_note + 1, __hip_atomic_load(&a.st->far_tiles, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(a.host_note + 1, far_tiles, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
         __hip_atomic_store(&a.st->far_tiles, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        /* Sdf::counter_ as the NEXT update() will see it (this launch's increment included: tile (0, 0) arrived before this
-         * workgroup read the ticket).  The normals stage used to take this snapshot; in GT-pose mode it now runs on its own
-         * stream beside this kernel and must not touch state the fusion uses. */
-        a.st->frame_cur = __hip_atomic_load(&a.st->frames, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (a.use_dev_pose) fuse_log_row(a);
+        a.st->frame_cur = frames;
+        GSDF_TRACE(a, ltr, 3);
+        /* (the frame's log row was written at the front of the launch: fuse_log_row) */
+    }
+    if (GSDF_EXPERIMENT(a.debug, 64)) {                               /* every wave's adds and thread 0's stores have left */
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        GSDF_TRACE(a, ltr, 4);
     }
 }
 
