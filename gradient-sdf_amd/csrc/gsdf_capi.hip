@@ -1232,9 +1232,14 @@ int gsdf_ba_setup(gsdf_ctx* c, int n, const float* images_bgr_host, const float*
     if (c->map_type != GSDF_MAP_GRAD) return fail(GSDF_ERR_INVALID, "PhotoBA needs the Gradient-SDF map (a base-sdf context has no gradient)");
     if (!c->map.vis) return fail(GSDF_ERR_INVALID, "PhotoBA needs the vis_ bit-vectors: call gsdf_enable_vis before fusing");
     if (n <= 0 || n > 64 || !images_bgr_host || !poses16_host || !frame_idx) return fail(GSDF_ERR_INVALID, "bad argument (1..64 keyframes)");
+    /* what the sweeps cannot index: ba_visible turns an id into a word and a bit of vis_ (a negative one lies in front of the
+     * buffer), and computeImageGradient's border branch reads column / row -1 of an image with fewer than 2 */
+    for (int i = 0; i < n; ++i)
+        if (frame_idx[i] < 0) return fail(GSDF_ERR_INVALID, "frame_idx: keyframe ids must be >= 0");
+    if (c->W < 2 || c->H < 2) return fail(GSDF_ERR_INVALID, "PhotoBA needs frames of at least 2 x 2 pixels (the image gradient reads a neighbour)");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->ba = gsdf_ba_bufs();                                   /* the old setup goes first; until the commit below there is none */
+    c->ba = gsdf_ba_bufs();                                  /* the old setup goes first; until the commit below there is none */
     c->ba_n = 0; c->ba_gate_fresh = false; c->ba_mean_valid = false; c->ba_pose_step = 0;
     gsdf_ba_bufs b;
     const size_t img_count = (size_t)n * c->W * c->H * 3;

@@ -235,6 +235,10 @@ int gsdf_export_vis(gsdf_ctx* c, int32_t* keys, uint32_t* words, int words_per_v
  * set has to be optimised in windows of <= 64 keyframes (the energy is a sum over voxels of terms that couple only the keyframes
  * that see the voxel, so windows of neighbouring keyframes are the usual bundle-adjustment practice -- but it is NOT what the
  * reference computes for n > 64, and no such windowing is done inside the library).
+ * Also GSDF_ERR_INVALID, checked before anything is allocated or launched (an earlier setup stays as it is): a negative
+ * frame_idx[i] (an id is a bit position of vis_), and a context whose frames have W < 2 or H < 2 (computeImageGradient, :80-140,
+ * reads a neighbouring column / row; the reference reads outside such an image).  An id at or beyond the frames of
+ * gsdf_enable_vis, or one that was never fused, is legal: that keyframe sees no voxel and its pose stays.
  * gsdf_ba_energy = getEnergy (:273-321), gsdf_ba_solve_pose = solvePose (:499-590), gsdf_ba_solve_dist =
  * solveDist (:326-388), gsdf_ba_optimize = optimize (:611-662): energies receives E0 and E after every pose
  * and distance step (<= 2*max_it+1 values), *converged = relative change < 5e-4. */
