@@ -156,6 +156,10 @@ def load(path=None):
         "gsdf_merge_raw_dev": (C.c_int, [vp, vp, vp, C.c_int64]),
         "gsdf_query": (C.c_int, [vp, fp, C.c_int64, fp, fp, fp]),
         "gsdf_get_voxels": (C.c_int, [vp, i32p, C.c_int64, fp, i32p]),
+        "gsdf_align_points": (C.c_int, [vp, fp, C.c_int64, fp, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int), fp]),
+        "gsdf_align_points_dev": (C.c_int, [vp, vp, C.c_int64, fp, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int), fp]),
+        "gsdf_surface_cloud": (C.c_int, [vp, fp, C.c_int64, i64p]),
+        "gsdf_surface_cloud_dev": (C.c_int, [vp, vp, C.c_int64, i64p]),
         "gsdf_block_keys_dev": (C.c_int, [vp, vp, C.c_int64, C.POINTER(C.c_int64)]),
         "gsdf_pack_blocks_dev": (C.c_int, [vp, vp, C.c_int64, vp]),
         "gsdf_unpack_blocks_dev": (C.c_int, [vp, vp, C.c_int64, vp]),
@@ -218,7 +222,8 @@ ABI_SYMBOLS = [
     "gsdf_merge_raw_dev", "gsdf_block_keys_dev", "gsdf_pack_blocks_dev", "gsdf_unpack_blocks_dev",
     "gsdf_merge_allreduce", "gsdf_merge_allreduce_with", "gsdf_rccl_unique_id", "gsdf_rccl_comm_init", "gsdf_rccl_comm_count",
     "gsdf_rccl_comm_destroy",
-    "gsdf_query", "gsdf_get_voxels", "gsdf_raycast", "gsdf_raycast_dev", "gsdf_raycast_counters", "gsdf_extract_mesh",
+    "gsdf_query", "gsdf_get_voxels", "gsdf_align_points", "gsdf_align_points_dev", "gsdf_surface_cloud", "gsdf_surface_cloud_dev",
+    "gsdf_raycast", "gsdf_raycast_dev", "gsdf_raycast_counters", "gsdf_extract_mesh",
     "gsdf_extract_mesh_indexed", "gsdf_mesh_components", "gsdf_extract_mesh_indexed_filtered", "gsdf_gradient_angles", "gsdf_gradient_stats",
     "gsdf_dev_alloc", "gsdf_dev_free", "gsdf_dev_upload", "gsdf_dev_download", "gsdf_timer_start", "gsdf_timer_stop_ms",
     "gsdf_host_alloc", "gsdf_host_free", "gsdf_dev_upload_async", "gsdf_mark", "gsdf_mark_wait", "gsdf_mark_reached",
@@ -695,6 +700,43 @@ class GradSdf:
         self._chk(self.L.gsdf_get_voxels(self.h, k.ctypes.data_as(C.POINTER(C.c_int32)), n, _fp(pay),
                                          found.ctypes.data_as(C.POINTER(C.c_int32))))
         return pay, found.astype(bool)
+
+    # -- registration of a point set, surface cloud ------------------------------------------------
+    def _align(self, fn, pts_arg, n, pose7, iters, conv, damping):
+        p = _f32(pose7).reshape(7).copy()
+        flag, passes = C.c_int(0), C.c_int(0)
+        trace = np.zeros((max(int(iters), 1), 36), np.float32)
+        self._chk(fn(self.h, pts_arg, int(n), _fp(p), int(iters), np.float32(conv), np.float32(damping), C.byref(flag),
+                     C.byref(passes), _fp(trace)))
+        return bool(flag.value), p, passes.value, trace[:passes.value]
+
+    def align_points(self, pts, pose7, iters=25, conv=1e-3, damping=1.0):
+        """gsdf_align_points: RigidPointOptimizer's Gauss-Newton loop over the points `pts` [n, 3] (source frame) from the pose
+        `pose7` (source -> map).  Returns (converged, pose7, passes, trace [passes, 36]); trace rows as the oracle's track()."""
+        x = _f32(pts).reshape(-1, 3)
+        return self._align(self.L.gsdf_align_points, _fp(x) if len(x) else None, len(x), pose7, iters, conv, damping)
+
+    def align_points_dev(self, pts_dev, n, pose7, iters=25, conv=1e-3, damping=1.0):
+        """the same over n x 3 floats already in device memory (a pointer from upload / dev_alloc, of this context or of another
+        one on the same device)"""
+        p = pts_dev if isinstance(pts_dev, C.c_void_p) or pts_dev is None else C.c_void_p(int(pts_dev))
+        return self._align(self.L.gsdf_align_points_dev, p, n, pose7, iters, conv, damping)
+
+    def surface_cloud(self):
+        """gsdf_surface_cloud: MapGradPixelSdf::extract_pc's rows [n, 6] = x y z nx ny nz, in (z, y, x) key order"""
+        n = C.c_int64(0)
+        self._chk(self.L.gsdf_surface_cloud(self.h, None, 0, C.byref(n)))
+        rows = np.empty((n.value, 6), np.float32)
+        if n.value:
+            self._chk(self.L.gsdf_surface_cloud(self.h, _fp(rows), n.value, C.byref(n)))
+        return rows
+
+    def surface_cloud_dev(self, rows_dev, max_n):
+        """gsdf_surface_cloud_dev: the rows into max_n x 6 floats of device memory; returns the row count (None / 0: sizing)"""
+        n = C.c_int64(0)
+        p = rows_dev if isinstance(rows_dev, C.c_void_p) or rows_dev is None else C.c_void_p(int(rows_dev))
+        self._chk(self.L.gsdf_surface_cloud_dev(self.h, p, int(max_n), C.byref(n)))
+        return n.value
 
     def raycast(self, R, t, zmin=0.5, zmax=3.5, W=None, H=None, K=None, normals=True):
         """Voxel-hash raycaster: (depth[H,W] camera z, 0 = no hit; normals[3,H,W] camera frame or None)."""

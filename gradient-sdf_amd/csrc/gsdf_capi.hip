@@ -1596,6 +1596,128 @@ int gsdf_get_voxels(gsdf_ctx* c, const int32_t* keys_host, int64_t n, float* pay
     return GSDF_OK;
 }
 
+/* RigidPointOptimizer.cpp:51-96 over points already on the device.  Pairs of pass + head are queued in batches (both kernels
+ * return at once when the run has ended); the host reads the run's small state once per batch, never per pass. */
+static int align_points_impl(gsdf_ctx* c, const float* pts_dev, int64_t n, float pose7[7], int num_iterations, float conv_threshold,
+                             float damping, int* converged, int* passes, float* trace36) {
+    const size_t part_bytes = (size_t)GSDF_ALIGN_MAXBLK * GSDF_ALIGN_ROW * sizeof(double);
+    HIP_TRY(c->align.grow(256 + part_bytes));
+    gsdf_align_state* d_st = c->align.as<gsdf_align_state>();
+    double* d_part = (double*)(c->align.as<char>() + 256);
+    gsdf_dev<float> d_trace;
+    if (trace36) HIP_TRY(d_trace.alloc((size_t)num_iterations * 36));
+    gsdf_align_state h;
+    std::memcpy(h.pose7, pose7, sizeof(h.pose7));
+    h.done = 0; h.converged = 0; h.passes = 0;
+    HIP_TRY(hipMemcpyAsync(d_st, &h, sizeof(h), hipMemcpyHostToDevice, c->stream));
+    const float conv_sq = conv_threshold * conv_threshold;                 /* RigidOptimizer.h:72 */
+    int queued = 0;
+    while (queued < num_iterations) {
+        const int batch = std::min(num_iterations - queued, queued == 0 ? c->first_batch : c->next_batch);
+        for (int k = 0; k < batch; ++k)
+            gsdf_launch_align_pass(c->stream, c->tab, c->voxel_size, c->voxel_size_inv, pts_dev, n, d_st, d_part, conv_sq, damping,
+                                   num_iterations, d_trace);
+        HIP_TRY(hipGetLastError());
+        queued += batch;
+        HIP_TRY(hipMemcpyAsync(&h, d_st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (h.done) break;
+    }
+    if (trace36 && h.passes > 0) {
+        HIP_TRY(hipMemcpyAsync(trace36, d_trace, (size_t)h.passes * 36 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    std::memcpy(pose7, h.pose7, sizeof(h.pose7));
+    *converged = h.converged;
+    *passes = h.passes;
+    return GSDF_OK;
+}
+
+static int align_points_check(gsdf_ctx* c, const float* pts, int64_t n, const float* pose7, int num_iterations, const int* converged,
+                              const int* passes) {
+    if (!c || !pose7 || !converged || !passes) return fail(GSDF_ERR_INVALID, "gsdf_align_points: null argument");
+    if (n < 0 || num_iterations < 0) return fail(GSDF_ERR_INVALID, "gsdf_align_points: negative n or num_iterations");
+    if (n > 0 && !pts) return fail(GSDF_ERR_INVALID, "gsdf_align_points: null points");
+    if (c->map_type == GSDF_MAP_BASE)
+        return fail(GSDF_ERR_INVALID, "gsdf_align_points: not available on a base-sdf context (it reads the stored gradient)");
+    return GSDF_OK;
+}
+
+int gsdf_align_points_dev(gsdf_ctx* c, const float* pts_dev, int64_t n, float pose7[7], int num_iterations, float conv_threshold,
+                          float damping, int* converged, int* passes, float* trace36) {
+    GSDF_FLUSH(c);
+    if (int rc = align_points_check(c, pts_dev, n, pose7, num_iterations, converged, passes)) return rc;
+    *converged = 0; *passes = 0;
+    if (num_iterations == 0) return GSDF_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    return align_points_impl(c, pts_dev, n, pose7, num_iterations, conv_threshold, damping, converged, passes, trace36);
+}
+
+int gsdf_align_points(gsdf_ctx* c, const float* pts_host, int64_t n, float pose7[7], int num_iterations, float conv_threshold,
+                      float damping, int* converged, int* passes, float* trace36) {
+    GSDF_FLUSH(c);
+    if (int rc = align_points_check(c, pts_host, n, pose7, num_iterations, converged, passes)) return rc;
+    *converged = 0; *passes = 0;
+    if (num_iterations == 0) return GSDF_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    gsdf_dev<void> big;
+    float* d = nullptr;
+    if (int rc = batch_scratch(c, (size_t)n * 3 * sizeof(float), big, (void**)&d)) return rc;
+    if (n > 0) HIP_TRY(hipMemcpyAsync(d, pts_host, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    return align_points_impl(c, d, n, pose7, num_iterations, conv_threshold, damping, converged, passes, trace36);
+}
+
+/* MapGradPixelSdf::extract_pc's rows (MapGradPixelSdf.cpp:182-195) into `out_dev` (rows_dev != nullptr) or `rows_host` */
+static int surface_cloud_impl(gsdf_ctx* c, float* rows_host, float* rows_dev, int64_t max_n, int64_t* n_out) {
+    if (!c || !n_out || max_n < 0) return fail(GSDF_ERR_INVALID, "gsdf_surface_cloud: bad argument");
+    if (c->map_type == GSDF_MAP_BASE)
+        return fail(GSDF_ERR_INVALID, "gsdf_surface_cloud: not available on a base-sdf context (extract_pc is MapGradPixelSdf's)");
+    HIP_TRY(hipSetDevice(c->device));
+    unsigned long long cnt = 0;
+    HIP_TRY(hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream));
+    gsdf_launch_surface_flag(c->stream, c->tab, c->n_slots, c->voxel_size, nullptr, nullptr, c->counter, 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&cnt, c->counter, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *n_out = (int64_t)cnt;
+    if (cnt == 0 || max_n == 0 || (!rows_host && !rows_dev)) return GSDF_OK;      /* nothing to write; the sizing call */
+    if ((int64_t)cnt > max_n) return fail(GSDF_ERR_INVALID, "gsdf_surface_cloud: max_n too small (*n holds the need)");
+    const size_t n = (size_t)cnt;
+    gsdf_dev<unsigned long long> ukeys, skeys;
+    gsdf_dev<uint32_t> uslots, sslots;
+    gsdf_dev<float> rows;
+    gsdf_dev<void> tmp;
+    HIP_TRY(ukeys.alloc(n));
+    HIP_TRY(skeys.alloc(n));
+    HIP_TRY(uslots.alloc(n));
+    HIP_TRY(sslots.alloc(n));
+    if (!rows_dev) HIP_TRY(rows.alloc(n * 6));
+    size_t tb = 0;
+    HIP_TRY(gsdf_sort_pairs_u64(nullptr, &tb, ukeys, skeys, uslots, sslots, n, c->stream));
+    HIP_TRY(tmp.alloc(std::max<size_t>(tb, 8)));
+    HIP_TRY(hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream));
+    gsdf_launch_surface_flag(c->stream, c->tab, c->n_slots, c->voxel_size, ukeys, uslots, c->counter, (long long)n);
+    HIP_TRY(hipGetLastError());
+    tb = tmp.bytes();
+    HIP_TRY(gsdf_sort_pairs_u64(tmp, &tb, ukeys, skeys, uslots, sslots, n, c->stream));
+    float* out = rows_dev ? rows_dev : rows.get();
+    gsdf_launch_surface_rows(c->stream, c->tab, c->voxel_size, skeys, sslots, n, out);
+    HIP_TRY(hipGetLastError());
+    if (rows_host) HIP_TRY(hipMemcpyAsync(rows_host, out, n * 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return GSDF_OK;
+}
+
+int gsdf_surface_cloud(gsdf_ctx* c, float* rows6_host, int64_t max_n, int64_t* n) {
+    GSDF_FLUSH(c);
+    return surface_cloud_impl(c, rows6_host, nullptr, max_n, n);
+}
+
+int gsdf_surface_cloud_dev(gsdf_ctx* c, float* rows6_dev, int64_t max_n, int64_t* n) {
+    GSDF_FLUSH(c);
+    return surface_cloud_impl(c, nullptr, rows6_dev, max_n, n);
+}
+
 static int raycast_enqueue(gsdf_ctx* c, const float K[9], const float R[9], const float t[3], int W, int H, float zmin, float zmax,
                            float* depth_dev, float* normals_dev) {
     gsdf_pose_arg pose;

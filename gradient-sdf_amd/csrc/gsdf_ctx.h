@@ -220,6 +220,7 @@ struct gsdf_ctx {
     long long rc_iters[2] = { 0, 0 };              /* loop iterations of the workgroups' wave 0 as of the last gsdf_raycast_counters */
     bool fuse_head = true;                         /* the frame's first fusion launch performs the head of the first batch's last tracker launch (GSDF_FUSE_HEAD) */
     gsdf_dev<void> scratch;                        /* device scratch of gsdf_query / gsdf_get_voxels for small batches (GSDF_SCRATCH_BYTES) */
+    gsdf_dev<void> align;                          /* gsdf_align_points: the run's state, then the partial rows (allocated by the first call) */
     bool occ_dirty = false;                        /* blocks may have been inserted since the raycaster's filters (gsdf_table::occ) were built */
     /* the reference's map grows without bound (MapGradPixelSdf.h:65-68); here: gsdf_grow, or by itself when gsdf_set_auto_grow
      * named a limit -- every few fusions the number of existing blocks is counted into a pinned word, and a frame entry that

@@ -181,6 +181,29 @@ void gsdf_launch_query(hipStream_t s, gsdf_table tab, float vs, float inv_vs, co
                        float* dist, float* grad, float* w, float base_T = -1.f /* >= 0: MapPixelSdf query with truncation T */);
 void gsdf_launch_get_voxels(hipStream_t s, gsdf_table tab, const int32_t* keys, long long n, float* payload, int32_t* found);
 
+/* Registration of a point set (gsdf_align.hip): RigidPointOptimizer.cpp:51-96 over n given points.  The run's state lives on the
+ * device; one call queues k_align_pass (the 29 sums of GSDF_TRACK_NSUM per workgroup into part) and k_align_head (totals in
+ * workgroup order, exact solve, stop test, pose update, trace row `passes`, nullable).  Both return at once when st->done is
+ * set, so pairs may be queued beyond the end of the run.  The grid is a function of n alone: gsdf_align_grid(n) workgroups. */
+#define GSDF_ALIGN_BLOCK   256
+#define GSDF_ALIGN_MAXBLK  512    /* workgroups of a pass at most: the head adds their rows one after the other */
+#define GSDF_ALIGN_ROW     32     /* doubles per partial row (29 used) */
+struct gsdf_align_state {
+    float pose7[7];
+    int done, converged, passes;
+};
+int  gsdf_align_grid(long long n);
+void gsdf_launch_align_pass(hipStream_t s, gsdf_table tab, float vs, float inv_vs, const float* pts, long long n,
+                            gsdf_align_state* st, double* part /* GSDF_ALIGN_MAXBLK x GSDF_ALIGN_ROW */, float conv_sq, float damping,
+                            int max_passes, float* trace /* nullable: max_passes x 36 */);
+/* The surface cloud (MapGradPixelSdf::extract_pc, MapGradPixelSdf.cpp:182-195): flag = packed key and slot of every voxel that
+ * passes the gates, appended through `counter` (keys == nullptr: count only); rows = the 6-float rows from the slots in sorted
+ * key order (the caller sorts the pairs with gsdf_sort_pairs_u64) */
+void gsdf_launch_surface_flag(hipStream_t s, gsdf_table tab, size_t n_slots, float vs, unsigned long long* keys, uint32_t* slots,
+                              unsigned long long* counter, long long max_n);
+void gsdf_launch_surface_rows(hipStream_t s, gsdf_table tab, float vs, const unsigned long long* skeys, const uint32_t* sslots, size_t n,
+                              float* rows6);
+
 void gsdf_launch_raycast(hipStream_t s, gsdf_table tab, float vs, float inv_vs, int factor /* band half-width in voxels */, int W, int H, const float K[9],
                          const gsdf_pose_arg& pose, float zmin, float zmax, float* depth_dev, float* normals_dev_or_null,
                          unsigned long long* wg_counts /* nullable: [workgroups of the 16x16-pixel grid][8]: samples, records, fast / slow loop iterations of wave 0 (added to); start / end tick of the workgroup */,

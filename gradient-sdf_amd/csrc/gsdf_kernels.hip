@@ -32,6 +32,7 @@
  * bands << 32 | list entries of the tile's flush << 36 */
 #define GSDF_TRACE_LAST_ROW 2047
 #include "gsdf_math.h"
+#include "gsdf_sample.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -2446,19 +2447,9 @@ __global__ __launch_bounds__(256) void k_query(gsdf_table tab, float vs, float i
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (; i < n; i += stride) {
         const gsdf_v3 p = { pts[3 * i], pts[3 * i + 1], pts[3 * i + 2] };
-        const int vx = gsdf_float2vox1(inv_vs, p.x), vy = gsdf_float2vox1(inv_vs, p.y), vz = gsdf_float2vox1(inv_vs, p.z);
-        float ow = 0.f, od = 0.f;
-        gsdf_v3 og = { 0.f, 0.f, 0.f };
-        if (gsdf_key_in_range(vx, vy, vz)) {
-            const gsdf_payload* sl = gsdf_find(tab, gsdf_key_pack(vx, vy, vz));
-            if (sl && sl->w > 0.f) {
-                ow = sl->w;
-                const gsdf_v3 gn = gsdf_normalized3(gsdf_v3{ sl->gx, sl->gy, sl->gz });
-                og = gsdf_v3{ 1.2f * gn.x, 1.2f * gn.y, 1.2f * gn.z };
-                const gsdf_v3 d = { vs * (float)vx - p.x, vs * (float)vy - p.y, vs * (float)vz - p.z };
-                od = gsdf_tsdf_phi(sl->s / sl->w, gn, d);                                  /* :114 */
-            }
-        }
+        float ow, od;
+        gsdf_v3 og;
+        gsdf_grad_sample(tab, vs, inv_vs, p, ow, od, og);                 /* gsdf_sample.h: shared with k_align_pass */
         w[i] = ow; dist[i] = od;
         grad[3 * i] = og.x; grad[3 * i + 1] = og.y; grad[3 * i + 2] = og.z;
     }

@@ -135,6 +135,12 @@ SdfVoxel MapGradPixelSdf::getSdf(Vec3i idx) const {
 /* extract_pc / save_sdf / extract_mesh -- MapGradPixelSdf.cpp:124-296: the writers live in exports.cpp (also reachable
  * from C through capi_host.cpp for hosts that hold a bare gsdf_ctx) */
 bool MapGradPixelSdf::extract_pc(std::string filename) { return gsdf_exports::write_cloud_ply(ctx_, voxel_size_, filename, nullptr); }
+bool MapGradPixelSdf::surface_cloud(std::vector<float>& rows6) const {
+    int64_t n = 0;
+    if (gsdf_surface_cloud(ctx_, nullptr, 0, &n) != GSDF_OK) return false;
+    rows6.assign((size_t)n * 6, 0.f);
+    return n == 0 || gsdf_surface_cloud(ctx_, rows6.data(), n, &n) == GSDF_OK;
+}
 bool MapGradPixelSdf::save_sdf(std::string filename) { return gsdf_exports::write_sdf_txt(ctx_, voxel_size_, filename); }
 bool MapGradPixelSdf::extract_mesh(std::string filename) { return gsdf_exports::write_mesh_ply(ctx_, voxel_size_, filename, nullptr); }
 bool MapGradPixelSdf::extract_mesh_indexed(std::string filename) { return gsdf_exports::write_indexed_mesh_ply(ctx_, filename, nullptr, nullptr); }

@@ -54,6 +54,9 @@ public:
     void raycast(const Mat3f& K, const SE3& pose, int W, int H, float* depth_out, float* normals_out) const;
 
     bool extract_pc(std::string filename) override;                    /* MapGradPixelSdf.cpp:177-220 */
+    /* extract_pc's rows (MapGradPixelSdf.cpp:182-195) in memory: x y z nx ny nz per row, (z, y, x) key order (gsdf_surface_cloud);
+     * false on a MapPixelSdf or an error (gsdf_last_error) */
+    bool surface_cloud(std::vector<float>& rows6) const;
     bool save_sdf(std::string filename) override;                      /* MapGradPixelSdf.cpp:222-296 */
     bool extract_mesh(std::string filename) override;                  /* MapGradPixelSdf.cpp:124-175 */
     /* the same surface as an indexed mesh with a gradient normal per vertex, binary PLY (gsdf_extract_mesh_indexed; not in the

@@ -38,6 +38,10 @@ public:
     bool optimize_sampled(const DepthImage& depth, const Mat3f K, size_t sampling);
     /* optimize() -> optimize_sampled(depth, K, 1) -- RigidPointOptimizer.h:69-72 */
     bool optimize(const DepthImage& depth, const Mat3f K) override { return optimize_sampled(depth, K, 1); }
+    /* The same Gauss-Newton loop (.cpp:51-96) over n points x y z the caller brings instead of the pixels of :62-69
+     * (gsdf_align_points): pose_ is the start (source -> map) and receives the result; num_iterations_, conv_threshold_ and
+     * damping_ as in optimize().  A MapPixelSdf is refused (std::runtime_error). */
+    bool optimize_points(const float* xyz, size_t n);
     int last_passes() const { return last_passes_; }
 };
 

@@ -435,6 +435,49 @@ int gsdf_query(gsdf_ctx* c, const float* pts_host, int64_t n, float* dist, float
  * found[i] == 0 marks a missing voxel (payload zeros; the reference's .at() would throw). */
 int gsdf_get_voxels(gsdf_ctx* c, const int32_t* keys_host, int64_t n, float* payload, int32_t* found);
 
+/* REGISTRATION OF A POINT SET against the map -- the loop of RigidPointOptimizer::optimize_sampled
+ * (RigidPointOptimizer.cpp:51-96) over n points the caller brings instead of the back-projected pixels of :62-69: from :70 on
+ * the reference's tracker never looks at the depth image again.  A second session's cloud, a LiDAR sweep, the vertices of a CAD
+ * part: anything that is to be brought into the map's frame (e.g. in front of gsdf_merge_from, which needs both maps in one).
+ * pts: n rows x y z (float32) in the source frame; every coordinate must be finite.  pose7 in/out (tx ty tz qx qy qz qw, unit
+ * quaternion): source -> map.  The context's persistent pose (gsdf_set_pose / gsdf_get_pose), the frame log and gsdf_stats are
+ * neither read nor written.
+ * One pass, per point: R = rotationMatrix() (:53); p = R x + t (:70); then exactly what gsdf_query returns for p -- weights() and
+ * tsdf() of MapGradPixelSdf.h:109-125 -- and, where w > 0, the terms phi^2, phi J[i], J[i] J[j] with J = (g, p x g) (:76-80) and
+ * the count (:81).  A point whose voxel is missing, beyond the key range or of weight 0 contributes nothing; a point that is not
+ * finite after the transform is skipped before the float -> int conversion of float2vox (the reference would convert it, which
+ * is undefined).  The float terms are widened to double and added in an order that depends on n alone (no floating-point
+ * atomics: the same call gives the same bytes, run to run and across gsdf_grow); each of the 29 sums is rounded to float once.
+ * Then xi = damping * H.llt().solve(g) (:86) with correctly rounded roots and divisions, |xi|^2 = (x0 + (x1 + x2)) + (x3 + (x4 +
+ * x5)); |xi|^2 < conv_threshold^2 ends the run converged without applying xi (:88-91); otherwise, unless a component is NaN,
+ * pose = SE3::exp(-xi) * pose (:94-95).
+ * *converged receives the bool the reference returns, *passes the reduction passes executed (k + 1 when converged at k, else
+ * num_iterations), as gsdf_track counts them.  trace36 (nullable, num_iterations x 36 floats) receives one row per executed
+ * pass: E, g[6], H upper triangle[21] row-major, count, xi[6] (damped), |xi|^2.
+ * n == 0 (pts may be NULL) behaves like an empty map: H = 0, xi NaN, not converged, *passes = num_iterations, pose7 unchanged.
+ * num_iterations == 0: *converged = 0, *passes = 0.  GSDF_ERR_INVALID: n < 0, num_iterations < 0, a NULL pose7 / converged /
+ * passes, NULL pts with n > 0, and a base-sdf context (the trilinear gather of MapPixelSdf is not built for point sets).
+ * Synchronous; a waiting pipelined fusion is launched first.  The _dev variant reads n x 3 contiguous floats of DEVICE memory in place (any
+ * buffer of gsdf_dev_alloc of a context on the same device, this one or another); the buffer must stay unchanged until the
+ * call returns.  Multi-GPU: not built -- the points and the map live on one device. */
+int gsdf_align_points(gsdf_ctx* c, const float* pts_host, int64_t n, float pose7[7],
+                      int num_iterations, float conv_threshold, float damping,
+                      int* converged, int* passes, float* trace36 /* nullable */);
+int gsdf_align_points_dev(gsdf_ctx* c, const float* pts_dev, int64_t n, float pose7[7],
+                          int num_iterations, float conv_threshold, float damping,
+                          int* converged, int* passes, float* trace36 /* nullable */);
+
+/* MapGradPixelSdf::extract_pc (MapGradPixelSdf.cpp:177-195) in memory instead of an ASCII PLY: one row x y z nx ny nz per voxel
+ * with weight >= 5 (:184) and |dist * 1.2 g^| < voxel_size / 2 on every axis (:186-188), point = vox2float(idx) - dist * 1.2 g^
+ * (:191), normal = -1.2 g^ (:192), all in float; g^ the normalised stored gradient sum.  The reference's row order is its hash
+ * map's; here rows follow the (z, y, x) key order of gsdf_export(sorted = 1).
+ * *n = rows of the cloud, always reported.  rows6 == NULL or max_n == 0 is the sizing call (nothing written, GSDF_OK); a max_n
+ * below the count writes nothing and returns GSDF_ERR_INVALID with the need in *n.  The _dev variant leaves the rows in the
+ * caller's DEVICE buffer (max_n x 6 floats), so that another context on the same device can read them without a host copy.
+ * Synchronous; the table is only read; a waiting pipelined fusion is launched first.  GSDF_ERR_INVALID on a base-sdf context. */
+int gsdf_surface_cloud(gsdf_ctx* c, float* rows6_host, int64_t max_n, int64_t* n);
+int gsdf_surface_cloud_dev(gsdf_ctx* c, float* rows6_dev, int64_t max_n, int64_t* n);
+
 /* Voxel-hash raycaster: depth (camera z, 0 = no hit) and camera-frame normals (3 planes, nullable) of the
  * fused map seen from pose (R, t) through K.  Named in BASELINE.json's north_star but ABSENT from the
  * reference: it is defined on top of Sdf::weights / Sdf::tsdf (MapGradPixelSdf.h:109-125) and the
