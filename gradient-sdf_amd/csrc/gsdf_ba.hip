@@ -287,9 +287,16 @@ struct ba_gate_pred {
         return !(fabsf(ws.y / ws.x) > vs);
     }
 };
-hipError_t gsdf_ba_compact(hipStream_t s, const gsdf_ba_dev& d, uint32_t* list_out, unsigned long long* count_out, void* tmp, size_t* tmp_bytes) {
+hipError_t gsdf_ba_compact_need(const gsdf_ba_dev& d, size_t* need) {
+    return gsdf_scratch_need(need, [&d](size_t& b) {
+        return rocprim::select(nullptr, b, rocprim::counting_iterator<uint32_t>(0u), (uint32_t*)nullptr, (unsigned long long*)nullptr, d.n_slots,
+                               ba_gate_pred{ d.tab.bkeys, d.tab.vox, d.vs }, hipStream_t());
+    });
+}
+hipError_t gsdf_ba_compact(const gsdf_dev<void>& tmp, hipStream_t s, const gsdf_ba_dev& d, uint32_t* list_out, unsigned long long* count_out) {
     const ba_gate_pred pred{ d.tab.bkeys, d.tab.vox, d.vs };
-    return rocprim::select(tmp, *tmp_bytes, rocprim::counting_iterator<uint32_t>(0u), list_out, count_out, d.n_slots, pred, s);
+    size_t b = tmp.bytes();
+    return rocprim::select(tmp.get(), b, rocprim::counting_iterator<uint32_t>(0u), list_out, count_out, d.n_slots, pred, s);
 }
 
 #define BA_BLOCKS 512

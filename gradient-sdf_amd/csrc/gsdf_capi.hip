@@ -11,6 +11,7 @@
 #include "gsdf_ctx.h"
 #include "gsdf_kernels.h"
 #include "gsdf_math.h"
+#include "gsdf_sweep.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1062,11 +1063,8 @@ int gsdf_count(gsdf_ctx* c, int64_t* n) {
     GSDF_FLUSH(c);
     if (!c || !n) return fail(GSDF_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream));
-    gsdf_launch_export(c->stream, c->tab, c->n_slots, nullptr, nullptr, c->counter, 0, 0, nullptr, 0, nullptr);
     unsigned long long h = 0;
-    HIP_TRY(hipMemcpyAsync(&h, c->counter, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(gsdf_counted(c, [&] { gsdf_launch_export(c->stream, c->tab, c->n_slots, nullptr, nullptr, c->counter, 0, 0, nullptr, 0, nullptr); }, &h));
     *n = (int64_t)h;
     return GSDF_OK;
 }
@@ -1115,7 +1113,7 @@ static int export_impl(gsdf_ctx* c, int32_t* keys, float* payload, uint32_t* vis
     HIP_TRY(dkeys.alloc((size_t)n));
     HIP_TRY(dpay.alloc((size_t)n * 5));
     if (vw) HIP_TRY(dvis.alloc((size_t)n * vw));
-    (void)hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream);
+    HIP_TRY(gsdf_counter_zero(c));
     gsdf_launch_export(c->stream, c->tab, c->n_slots, dkeys, dpay, c->counter, n, raw_sums, c->map.vis, vw, dvis);
     std::vector<unsigned long long> hk((size_t)n);
     std::vector<float> hp((size_t)n * 5);
@@ -1162,11 +1160,8 @@ int gsdf_export_raw_dev(gsdf_ctx* c, int32_t* keys_dev, float* payload_dev, int6
     GSDF_FLUSH(c);
     if (!c || !keys_dev || !payload_dev || max_n < 0) return fail(GSDF_ERR_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream));
-    gsdf_launch_export_raw(c->stream, c->tab, c->n_slots, keys_dev, payload_dev, c->counter, max_n);
     unsigned long long h = 0;
-    HIP_TRY(hipMemcpyAsync(&h, c->counter, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(gsdf_counted(c, [&] { gsdf_launch_export_raw(c->stream, c->tab, c->n_slots, keys_dev, payload_dev, c->counter, max_n); }, &h));
     if (n) *n = (int64_t)h;
     if ((int64_t)h > max_n) return fail(GSDF_ERR_INVALID, "export buffer too small (call gsdf_count first)");
     return GSDF_OK;
@@ -1201,8 +1196,7 @@ static gsdf_ba_dev ba_dev(gsdf_ctx* c) {
 static void ba_refresh_gate(gsdf_ctx* c) {
     if (c->ba_gate_fresh || !c->ba.gate_list || !c->ba.counter2) return;
     gsdf_ba_dev d = ba_dev(c);
-    size_t bytes = c->ba.gate_tmp.bytes();
-    if (gsdf_ba_compact(c->stream, d, c->ba.gate_list, c->ba.counter2, c->ba.gate_tmp, &bytes) == hipSuccess) c->ba_gate_fresh = true;
+    if (gsdf_ba_compact(c->ba.gate_tmp, c->stream, d, c->ba.gate_list, c->ba.counter2) == hipSuccess) c->ba_gate_fresh = true;
     else (void)hipGetLastError();
 }
 static int ba_upload_poses(gsdf_ctx* c) {
@@ -1253,8 +1247,8 @@ int gsdf_ba_setup(gsdf_ctx* c, int n, const float* images_bgr_host, const float*
     HIP_TRY(b.Hb.alloc((size_t)n * 27));
     {   /* the gate list of the energy / pose sweeps: optional (without it they sweep the whole table) */
         size_t bytes = 0;
-        if (gsdf_ba_compact(c->stream, ba_dev(c), nullptr, nullptr, nullptr, &bytes) == hipSuccess &&
-            b.gate_list.alloc(c->n_slots) == hipSuccess && b.gate_tmp.alloc(bytes ? bytes : 8) == hipSuccess && b.counter2.alloc(1) == hipSuccess) {
+        if (gsdf_ba_compact_need(ba_dev(c), &bytes) == hipSuccess &&
+            b.gate_list.alloc(c->n_slots) == hipSuccess && b.gate_tmp.alloc(bytes) == hipSuccess && b.counter2.alloc(1) == hipSuccess) {
             /* optional on top: 24 B per possible list entry for what the energy sweep hands to the pose sweep (100 MB at 2^22 records) */
             /* GSDF_BA_MEAN_CACHE (read here, so that a test can switch within one context): 0 the pose sweep computes its means
              * itself; 2 (tests only) the stand-alone gsdf_ba_solve_pose trusts that nothing changed since the last energy sweep */
@@ -1674,11 +1668,7 @@ static int surface_cloud_impl(gsdf_ctx* c, float* rows_host, float* rows_dev, in
         return fail(GSDF_ERR_INVALID, "gsdf_surface_cloud: not available on a base-sdf context (extract_pc is MapGradPixelSdf's)");
     HIP_TRY(hipSetDevice(c->device));
     unsigned long long cnt = 0;
-    HIP_TRY(hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream));
-    gsdf_launch_surface_flag(c->stream, c->tab, c->n_slots, c->voxel_size, nullptr, nullptr, c->counter, 0);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&cnt, c->counter, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(gsdf_counted(c, [&] { gsdf_launch_surface_flag(c->stream, c->tab, c->n_slots, c->voxel_size, nullptr, nullptr, c->counter, 0); }, &cnt));
     *n_out = (int64_t)cnt;
     if (cnt == 0 || max_n == 0 || (!rows_host && !rows_dev)) return GSDF_OK;      /* nothing to write; the sizing call */
     if ((int64_t)cnt > max_n) return fail(GSDF_ERR_INVALID, "gsdf_surface_cloud: max_n too small (*n holds the need)");
@@ -1692,14 +1682,13 @@ static int surface_cloud_impl(gsdf_ctx* c, float* rows_host, float* rows_dev, in
     HIP_TRY(uslots.alloc(n));
     HIP_TRY(sslots.alloc(n));
     if (!rows_dev) HIP_TRY(rows.alloc(n * 6));
-    size_t tb = 0;
-    HIP_TRY(gsdf_sort_pairs_u64(nullptr, &tb, ukeys, skeys, uslots, sslots, n, c->stream));
-    HIP_TRY(tmp.alloc(std::max<size_t>(tb, 8)));
-    HIP_TRY(hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream));
+    size_t need = 0;
+    HIP_TRY(gsdf_sort_pairs_u64_need(n, &need));
+    HIP_TRY(tmp.alloc(need));
+    HIP_TRY(gsdf_counter_zero(c));
     gsdf_launch_surface_flag(c->stream, c->tab, c->n_slots, c->voxel_size, ukeys, uslots, c->counter, (long long)n);
     HIP_TRY(hipGetLastError());
-    tb = tmp.bytes();
-    HIP_TRY(gsdf_sort_pairs_u64(tmp, &tb, ukeys, skeys, uslots, sslots, n, c->stream));
+    HIP_TRY(gsdf_sort_pairs_u64(tmp, ukeys, skeys, uslots, sslots, n, c->stream));
     float* out = rows_dev ? rows_dev : rows.get();
     gsdf_launch_surface_rows(c->stream, c->tab, c->voxel_size, skeys, sslots, n, out);
     HIP_TRY(hipGetLastError());
@@ -1804,29 +1793,18 @@ int gsdf_extract_mesh(gsdf_ctx* c, float iso, const int8_t tri_table[256 * 16], 
     const int big[3] = { 2147483647, 2147483647, 2147483647 };
     HIP_TRY(hipMemcpyAsync(d_mn, big, sizeof(big), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_tab, tri_table, 256 * 16, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream));
     unsigned long long n = 0;
-    gsdf_launch_mesh(c->stream, c->tab, c->n_slots, c->voxel_size, iso, d_mn, d_tab, d_tris, d_keys, c->counter, cap);
-    HIP_TRY(hipMemcpyAsync(&n, c->counter, sizeof(n), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(gsdf_counted(c, [&] { gsdf_launch_mesh(c->stream, c->tab, c->n_slots, c->voxel_size, iso, d_mn, d_tab, d_tris, d_keys, c->counter, cap); }, &n));
     const size_t got = (size_t)std::min<unsigned long long>(n, (unsigned long long)cap);
     /* the reference's order (z-y-x sweep, triangles of a cube in table order) = ascending sort key: radix sort of (key, index)
      * on the device, the triangles gathered into that order on the device, ONE copy of the sorted list to the caller */
     if (got && n <= (unsigned long long)cap) {
-        gsdf_dev<unsigned long long> d_keys2;
-        gsdf_dev<uint32_t> d_idx, d_idx2;
+        gsdf_key_order ord;
         gsdf_dev<float> d_sorted;
-        gsdf_dev<void> d_tmp;
-        size_t tmp_bytes = 0;
-        HIP_TRY(d_keys2.alloc(got));
-        HIP_TRY(d_idx.alloc(got));
-        HIP_TRY(d_idx2.alloc(got));
+        HIP_TRY(ord.alloc(got));
         HIP_TRY(d_sorted.alloc(got * 9));
-        HIP_TRY(gsdf_sort_pairs_u64(nullptr, &tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, got, c->stream));
-        HIP_TRY(d_tmp.alloc(tmp_bytes ? tmp_bytes : 8));
-        gsdf_launch_iota(c->stream, d_idx, got);
-        HIP_TRY(gsdf_sort_pairs_u64(d_tmp, &tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, got, c->stream));
-        gsdf_launch_gather_tris(c->stream, d_tris, d_idx2, d_sorted, got);
+        HIP_TRY(ord.run(c, d_keys, got));
+        gsdf_launch_gather_tris(c->stream, d_tris, ord.order, d_sorted, got);
         HIP_TRY(hipMemcpyAsync(triangles_out, d_sorted, got * 9 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
@@ -1848,10 +1826,10 @@ struct indexed_mesh_dev {
     gsdf_dev<int> mn;
     gsdf_dev<signed char> tab;
     gsdf_dev<float> tris, v, n;
-    gsdf_dev<unsigned long long> keys, keys2, ekeys, ck, ck2, vkeys;
-    gsdf_dev<uint32_t> muw, idx, order, rank, rank2, heads, before, vmuw;
+    gsdf_dev<unsigned long long> keys, ekeys, ck, ck2, vkeys;
+    gsdf_dev<uint32_t> muw, rank, rank2, heads, before, vmuw;
     gsdf_dev<int32_t> faces;
-    gsdf_dev<void> tmp;
+    gsdf_key_order soup;                                       /* the soup's order; its scratch also serves the corner sort and the heads scan */
     size_t nt = 0, nc = 0, nv = 0;                             /* faces, corners, vertices */
 };
 
@@ -1862,49 +1840,37 @@ int indexed_mesh_count(gsdf_ctx* c, float iso, const int8_t* tri_table, const ch
     const int big[3] = { 2147483647, 2147483647, 2147483647 };
     HIP_TRY(hipMemcpyAsync(m.mn, big, sizeof(big), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(m.tab, tri_table, 256 * 16, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream));
     unsigned long long n = 0, n2 = 0;
-    gsdf_launch_mesh(c->stream, c->tab, c->n_slots, c->voxel_size, iso, m.mn, m.tab, nullptr, nullptr, c->counter, 0);
-    HIP_TRY(hipMemcpyAsync(&n, c->counter, sizeof(n), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(gsdf_counted(c, [&] { gsdf_launch_mesh(c->stream, c->tab, c->n_slots, c->voxel_size, iso, m.mn, m.tab, nullptr, nullptr, c->counter, 0); }, &n));
     if (n == 0) return GSDF_OK;
     if (n > 2147483647ull / 3)
         return fail(GSDF_ERR_INVALID, std::string(who) + ": more than (2^31 - 1) / 3 triangles (vertex ids and corner ranks are 32-bit)");
     const size_t nt = (size_t)n, nc = 3 * nt;
     HIP_TRY(m.tris.alloc(nt * 9));
     HIP_TRY(m.keys.alloc(nt));
-    HIP_TRY(m.keys2.alloc(nt));
     HIP_TRY(m.ekeys.alloc(nc));
     HIP_TRY(m.muw.alloc(nc));
-    HIP_TRY(m.idx.alloc(nt));
-    HIP_TRY(m.order.alloc(nt));
     HIP_TRY(m.ck.alloc(nc));
     HIP_TRY(m.ck2.alloc(nc));
     HIP_TRY(m.rank.alloc(nc));
     HIP_TRY(m.rank2.alloc(nc));
     HIP_TRY(m.heads.alloc(nc));
     HIP_TRY(m.before.alloc(nc));
-    size_t b0 = 0, b1 = 0, b2 = 0;
-    HIP_TRY(gsdf_sort_pairs_u64(nullptr, &b0, m.keys, m.keys2, m.idx, m.order, nt, c->stream));
-    HIP_TRY(gsdf_sort_pairs_u64(nullptr, &b1, m.ck, m.ck2, m.rank, m.rank2, nc, c->stream));
-    HIP_TRY(gsdf_run_heads_scan(nullptr, &b2, m.ck2, m.heads, m.before, nc, c->stream));
-    HIP_TRY(m.tmp.alloc(std::max<size_t>(std::max(b0, b1), std::max<size_t>(b2, 8))));
-    HIP_TRY(hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream));
+    size_t need = 0;
+    HIP_TRY(gsdf_sort_pairs_u64_need(nc, &need));
+    HIP_TRY(gsdf_run_heads_scan_need(nc, &need));
+    HIP_TRY(m.soup.alloc(nt, need));
+    HIP_TRY(gsdf_counter_zero(c));
     gsdf_launch_mesh_corners(c->stream, c->tab, c->n_slots, c->voxel_size, iso, m.mn, m.tab, m.tris, m.keys, m.ekeys, m.muw, c->counter,
                              (long long)nt);
-    HIP_TRY(hipMemcpyAsync(&n2, c->counter, sizeof(n2), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(gsdf_counter_read(c, &n2));
     /* the soup's order, then the weld: stable sort of (edge key, corner rank), run starts, their scan */
-    gsdf_launch_iota(c->stream, m.idx, nt);
-    b0 = m.tmp.bytes();
-    HIP_TRY(gsdf_sort_pairs_u64(m.tmp, &b0, m.keys, m.keys2, m.idx, m.order, nt, c->stream));
-    gsdf_launch_corner_keys(c->stream, m.ekeys, m.order, m.ck, m.rank, nt);
-    b1 = m.tmp.bytes();
-    HIP_TRY(gsdf_sort_pairs_u64(m.tmp, &b1, m.ck, m.ck2, m.rank, m.rank2, nc, c->stream));
-    b2 = m.tmp.bytes();
-    HIP_TRY(gsdf_run_heads_scan(m.tmp, &b2, m.ck2, m.heads, m.before, nc, c->stream));
+    HIP_TRY(m.soup.run(c, m.keys, nt));
+    gsdf_launch_corner_keys(c->stream, m.ekeys, m.soup.order, m.ck, m.rank, nt);
+    HIP_TRY(gsdf_sort_pairs_u64(m.soup.tmp, m.ck, m.ck2, m.rank, m.rank2, nc, c->stream));
+    HIP_TRY(gsdf_run_heads_scan(m.soup.tmp, m.ck2, m.heads, m.before, nc, c->stream));
     uint32_t last[2] = { 0u, 0u };
-    HIP_TRY(hipMemcpyAsync(&last[0], m.before + (nc - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&last[1], m.heads + (nc - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(gsdf_scan_total_read(c->stream, m.before, m.heads, nc, last));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (n2 != n) return fail(GSDF_ERR_HIP, std::string(who) + ": the map changed between the counting and the corner pass");
@@ -1918,7 +1884,7 @@ int indexed_mesh_weld(gsdf_ctx* c, bool normals, indexed_mesh_dev& m) {
     HIP_TRY(m.vkeys.alloc(m.nv));
     HIP_TRY(m.vmuw.alloc(m.nv));
     if (normals) HIP_TRY(m.n.alloc(m.nv * 3));
-    gsdf_launch_weld(c->stream, m.ck2, m.rank2, m.heads, m.before, m.order, m.tris, m.muw, m.nc, m.faces, m.v, m.vkeys, m.vmuw);
+    gsdf_launch_weld(c->stream, m.ck2, m.rank2, m.heads, m.before, m.soup.order, m.tris, m.muw, m.nc, m.faces, m.v, m.vkeys, m.vmuw);
     if (normals) gsdf_launch_vertex_normals(c->stream, c->tab, m.mn, m.vkeys, m.vmuw, m.nv, m.n);
     HIP_TRY(hipGetLastError());
     return GSDF_OK;
@@ -1968,15 +1934,13 @@ int mesh_components_label(gsdf_ctx* c, const indexed_mesh_dev& m, bool boxes, me
     HIP_TRY(cc.before.alloc(nv));
     HIP_TRY(cc.vcomp.alloc(nv));
     HIP_TRY(cc.fcomp.alloc(nt));
-    size_t bytes = 0;
-    HIP_TRY(gsdf_scan_u32(nullptr, &bytes, cc.flags, cc.before, std::max(nv, nt), c->stream));
-    HIP_TRY(cc.tmp.alloc(std::max<size_t>(bytes, 8)));
+    size_t need = 0;
+    HIP_TRY(gsdf_scan_u32_need(std::max(nv, nt), &need));
+    HIP_TRY(cc.tmp.alloc(need));
     gsdf_launch_cc_label(c->stream, m.faces, nt, nv, cc.parent, cc.root, cc.flags);
-    bytes = cc.tmp.bytes();
-    HIP_TRY(gsdf_scan_u32(cc.tmp, &bytes, cc.flags, cc.before, nv, c->stream));
+    HIP_TRY(gsdf_scan_u32(cc.tmp, cc.flags, cc.before, nv, c->stream));
     uint32_t last[2] = { 0u, 0u };
-    HIP_TRY(hipMemcpyAsync(&last[0], cc.before + (nv - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&last[1], cc.flags + (nv - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(gsdf_scan_total_read(c->stream, cc.before, cc.flags, nv, last));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     cc.n_comp = (size_t)last[0] + last[1];
@@ -2053,16 +2017,12 @@ int gsdf_extract_mesh_indexed_filtered(gsdf_ctx* c, float iso, const int8_t tri_
     gsdf_launch_cc_keep(c->stream, cc.counts, cc.n_comp, (long long)min_faces, d_keep, d_kept);
     gsdf_launch_cc_keep_flags(c->stream, cc.vcomp, d_keep, nv, d_vflags);
     gsdf_launch_cc_keep_flags(c->stream, cc.fcomp, d_keep, nt, d_fflags);
-    size_t bytes = cc.tmp.bytes();
-    HIP_TRY(gsdf_scan_u32(cc.tmp, &bytes, d_vflags, d_vbefore, nv, c->stream));
-    bytes = cc.tmp.bytes();
-    HIP_TRY(gsdf_scan_u32(cc.tmp, &bytes, d_fflags, d_fbefore, nt, c->stream));
+    HIP_TRY(gsdf_scan_u32(cc.tmp, d_vflags, d_vbefore, nv, c->stream));
+    HIP_TRY(gsdf_scan_u32(cc.tmp, d_fflags, d_fbefore, nt, c->stream));
     uint32_t h[5] = { 0u, 0u, 0u, 0u, 0u };
     HIP_TRY(hipMemcpyAsync(&h[0], d_kept, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&h[1], d_vbefore + (nv - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&h[2], d_vflags + (nv - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&h[3], d_fbefore + (nt - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&h[4], d_fflags + (nt - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(gsdf_scan_total_read(c->stream, d_vbefore, d_vflags, nv, &h[1]));
+    HIP_TRY(gsdf_scan_total_read(c->stream, d_fbefore, d_fflags, nt, &h[3]));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     const size_t kv = (size_t)h[1] + h[2], kf = (size_t)h[3] + h[4];
@@ -2091,11 +2051,8 @@ int gsdf_block_keys_dev(gsdf_ctx* c, uint64_t* keys_dev, int64_t max_n, int64_t*
     GSDF_FLUSH(c);
     if (!c || !n || (max_n > 0 && !keys_dev)) return fail(GSDF_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream));
-    gsdf_launch_block_keys(c->stream, c->tab, c->n_slots / GSDF_BLOCK_VOX, (unsigned long long*)keys_dev, c->counter, max_n);
     unsigned long long cnt = 0;
-    HIP_TRY(hipMemcpyAsync(&cnt, c->counter, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(gsdf_counted(c, [&] { gsdf_launch_block_keys(c->stream, c->tab, c->n_slots / GSDF_BLOCK_VOX, (unsigned long long*)keys_dev, c->counter, max_n); }, &cnt));
     *n = (int64_t)cnt;
     return GSDF_OK;
 }

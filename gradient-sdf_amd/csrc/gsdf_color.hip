@@ -16,6 +16,7 @@
 #include "gsdf_interp.h"
 #include "gsdf_kernels.h"
 #include "gsdf_math.h"
+#include "gsdf_sweep.h"
 
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
@@ -208,6 +209,25 @@ __global__ __launch_bounds__(256) void k_cloud_emit(const unsigned long long* __
 
 static int cfail(int code, const std::string& msg) { return gsdf_fail(code, msg); }
 
+/* the selection (rocPRIM select over the slot numbers) and the cloud's prefix sum, as the X_need / X pairs of gsdf_kernels.h */
+static hipError_t color_select_need(const color_sel_pred& pred, size_t n_slots, size_t* need) {
+    return gsdf_scratch_need(need, [&](size_t& b) {
+        return rocprim::select(nullptr, b, rocprim::counting_iterator<uint32_t>(0u), (uint32_t*)nullptr, (unsigned long long*)nullptr, n_slots, pred, hipStream_t());
+    });
+}
+static hipError_t color_select(const gsdf_dev<void>& tmp, const color_sel_pred& pred, uint32_t* list, unsigned long long* count, size_t n_slots,
+                               hipStream_t s) {
+    size_t b = tmp.bytes();
+    return rocprim::select(tmp.get(), b, rocprim::counting_iterator<uint32_t>(0u), list, count, n_slots, pred, s);
+}
+static hipError_t color_scan_need(size_t n, size_t* need) {
+    return gsdf_scratch_need(need, [n](size_t& b) { return rocprim::exclusive_scan(nullptr, b, (uint32_t*)0, (uint32_t*)0, 0u, n, rocprim::plus<uint32_t>(), hipStream_t()); });
+}
+static hipError_t color_scan(const gsdf_dev<void>& tmp, uint32_t* counts, uint32_t* offsets, size_t n, hipStream_t s) {
+    size_t b = tmp.bytes();
+    return rocprim::exclusive_scan(tmp.get(), b, counts, offsets, 0u, n, rocprim::plus<uint32_t>(), s);
+}
+
 int gsdf_color_compute(gsdf_ctx* c, int n, const float* images_bgr_host, const float* poses16_host, const int* frame_idx,
                        int64_t* n_voxels) {
     if (!c) return cfail(GSDF_ERR_INVALID, "null context");
@@ -253,11 +273,10 @@ int gsdf_color_compute(gsdf_ctx* c, int n, const float* images_bgr_host, const f
     /* selection: the slots of the kept voxels, in slot order */
     const float gate = (float)(std::sqrt(3.) * c->voxel_size);                   /* init :143 */
     const color_sel_pred pred{ c->tab.bkeys, c->tab.vox, gate };
-    size_t bytes = 0;
-    HIP_TRY(rocprim::select(nullptr, bytes, rocprim::counting_iterator<uint32_t>(0u), S->list.get(), S->words.get(), c->n_slots, pred, c->stream));
-    HIP_TRY(S->tmp.grow(bytes));
-    bytes = S->tmp.bytes();
-    HIP_TRY(rocprim::select(S->tmp, bytes, rocprim::counting_iterator<uint32_t>(0u), S->list.get(), S->words.get(), c->n_slots, pred, c->stream));
+    size_t need = 0;
+    HIP_TRY(color_select_need(pred, c->n_slots, &need));
+    HIP_TRY(S->tmp.grow(need));
+    HIP_TRY(color_select(S->tmp, pred, S->list, S->words, c->n_slots, c->stream));
     unsigned long long N = 0;
     HIP_TRY(hipMemcpyAsync(&N, S->words, sizeof(N), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -268,11 +287,10 @@ int gsdf_color_compute(gsdf_ctx* c, int n, const float* images_bgr_host, const f
     HIP_TRY(S->rows.grow((size_t)N * GSDF_COLOR_ROW));
     if (N) {
         hipLaunchKernelGGL(k_color_keys, dim3((unsigned int)((N + 255) / 256)), dim3(256), 0, c->stream, S->list, c->tab.bkeys, S->keys_in, (size_t)N);
-        bytes = 0;
-        HIP_TRY(gsdf_sort_pairs_u64(nullptr, &bytes, S->keys_in, S->keys, S->list, S->slots, (size_t)N, c->stream));
-        HIP_TRY(S->tmp.grow(bytes));
-        bytes = S->tmp.bytes();
-        HIP_TRY(gsdf_sort_pairs_u64(S->tmp, &bytes, S->keys_in, S->keys, S->list, S->slots, (size_t)N, c->stream));
+        need = 0;
+        HIP_TRY(gsdf_sort_pairs_u64_need((size_t)N, &need));
+        HIP_TRY(S->tmp.grow(need));
+        HIP_TRY(gsdf_sort_pairs_u64(S->tmp, S->keys_in, S->keys, S->list, S->slots, (size_t)N, c->stream));
         color_args a;
         a.tab = c->tab; a.slots = S->slots; a.n_vox = (long long)N;
         a.vis = c->map.vis; a.vis_words = c->vis_words;
@@ -334,14 +352,12 @@ int gsdf_color_cloud(gsdf_ctx* c, float* rows9, int64_t max_n, int64_t* n) {
             HIP_TRY(S->offsets.grow(N));
             const dim3 grid((unsigned int)((N + 255) / 256));
             hipLaunchKernelGGL(k_cloud_count, grid, dim3(256), 0, c->stream, S->rows, N, vs4, S->counts);
-            size_t bytes = 0;
-            HIP_TRY(rocprim::exclusive_scan(nullptr, bytes, S->counts.get(), S->offsets.get(), 0u, N, rocprim::plus<uint32_t>(), c->stream));
-            HIP_TRY(S->tmp.grow(bytes));
-            bytes = S->tmp.bytes();
-            HIP_TRY(rocprim::exclusive_scan(S->tmp, bytes, S->counts.get(), S->offsets.get(), 0u, N, rocprim::plus<uint32_t>(), c->stream));
+            size_t need = 0;
+            HIP_TRY(color_scan_need(N, &need));
+            HIP_TRY(S->tmp.grow(need));
+            HIP_TRY(color_scan(S->tmp, S->counts, S->offsets, N, c->stream));
             uint32_t last[2] = { 0u, 0u };
-            HIP_TRY(hipMemcpyAsync(&last[0], S->offsets + N - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipMemcpyAsync(&last[1], S->counts + N - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(gsdf_scan_total_read(c->stream, S->offsets, S->counts, N, last));
             HIP_TRY(hipStreamSynchronize(c->stream));
             total = (unsigned long long)last[0] + last[1];
             HIP_TRY(S->cloud.grow((size_t)total * 9));
@@ -531,39 +547,27 @@ int gsdf_color_mesh(gsdf_ctx* c, float iso, float* triangles_out, uint8_t* color
     if (cap) HIP_TRY(d_cols.alloc((size_t)cap * 3));
     if (cap) HIP_TRY(d_keys.alloc((size_t)cap));
     HIP_TRY(hipMemcpyAsync(d_tab, GSDF_MC_TRI_TABLE, 256 * 16, hipMemcpyHostToDevice, c->stream));   /* the Hr triTable (:96-352) is the classic one */
-    HIP_TRY(hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream));
     hr_mesh_args a;
     a.keys = S->keys; a.rows = S->rows; a.n = S->n;
     for (int k = 0; k < 3; ++k) { a.mn[k] = box[k]; a.mx[k] = box[3 + k]; }
     a.vs = S->vs; a.iso = iso; a.tri_table = d_tab;
     a.tris = d_tris; a.cols = d_cols; a.skeys = d_keys; a.counter = c->counter; a.max_tris = cap;
-    hipLaunchKernelGGL(k_hr_mesh, dim3((unsigned int)((8 * N + 255) / 256)), dim3(256), 0, c->stream, a);
-    HIP_TRY(hipGetLastError());
     unsigned long long n = 0;
-    HIP_TRY(hipMemcpyAsync(&n, c->counter, sizeof(n), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(gsdf_counted(c, [&] { hipLaunchKernelGGL(k_hr_mesh, dim3((unsigned int)((8 * N + 255) / 256)), dim3(256), 0, c->stream, a); }, &n));
     /* the reference's order (fine z-y-x sweep, triangles of a cube in table order) = ascending sweep key, as gsdf_extract_mesh */
     if (n && n <= (unsigned long long)cap) {
         const size_t got = (size_t)n;
-        gsdf_dev<unsigned long long> d_keys2;
-        gsdf_dev<uint32_t> d_idx, d_idx2;
+        gsdf_key_order ord;
         gsdf_dev<float> d_sorted;
         gsdf_dev<uint8_t> d_bytes;
-        gsdf_dev<void> d_tmp;
-        size_t tmp_bytes = 0;
-        HIP_TRY(d_keys2.alloc(got));
-        HIP_TRY(d_idx.alloc(got));
-        HIP_TRY(d_idx2.alloc(got));
+        HIP_TRY(ord.alloc(got));
         HIP_TRY(d_sorted.alloc(got * 9));
-        HIP_TRY(gsdf_sort_pairs_u64(nullptr, &tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, got, c->stream));
-        HIP_TRY(d_tmp.alloc(tmp_bytes ? tmp_bytes : 8));
-        gsdf_launch_iota(c->stream, d_idx, got);
-        HIP_TRY(gsdf_sort_pairs_u64(d_tmp, &tmp_bytes, d_keys, d_keys2, d_idx, d_idx2, got, c->stream));
-        gsdf_launch_gather_tris(c->stream, d_tris, d_idx2, d_sorted, got);
+        HIP_TRY(ord.run(c, d_keys, got));
+        gsdf_launch_gather_tris(c->stream, d_tris, ord.order, d_sorted, got);
         HIP_TRY(hipMemcpyAsync(triangles_out, d_sorted, got * 9 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         if (colors_out) {
             HIP_TRY(d_bytes.alloc(got * 9));
-            hipLaunchKernelGGL(k_hr_gather_cols, dim3((unsigned int)((got * 9 + 255) / 256)), dim3(256), 0, c->stream, d_cols.get(), d_idx2.get(),
+            hipLaunchKernelGGL(k_hr_gather_cols, dim3((unsigned int)((got * 9 + 255) / 256)), dim3(256), 0, c->stream, d_cols.get(), ord.order.get(),
                                d_bytes.get(), got);
             HIP_TRY(hipMemcpyAsync(colors_out, d_bytes, got * 9, hipMemcpyDeviceToHost, c->stream));
         }

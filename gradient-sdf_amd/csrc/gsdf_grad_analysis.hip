@@ -26,6 +26,7 @@
 #include "gsdf_ctx.h"
 #include "gsdf_kernels.h"
 #include "gsdf_math.h"
+#include "gsdf_sweep.h"
 
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -236,9 +237,15 @@ __global__ __launch_bounds__(256) void k_grad_gather(const unsigned long long* _
     }
 }
 
-static hipError_t grad_sort_pairs_u32(void* tmp, size_t* tmp_bytes, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in,
+static hipError_t grad_sort_pairs_u32_need(size_t n, size_t* need) {
+    const uint32_t* in = nullptr;
+    uint32_t* out = nullptr;
+    return gsdf_scratch_need(need, [=](size_t& b) { return rocprim::radix_sort_pairs(nullptr, b, in, out, in, out, n, 0, 32, hipStream_t()); });
+}
+static hipError_t grad_sort_pairs_u32(const gsdf_dev<void>& tmp, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in,
                                       uint32_t* vals_out, size_t n, hipStream_t s) {
-    return rocprim::radix_sort_pairs(tmp, *tmp_bytes, keys_in, keys_out, vals_in, vals_out, n, 0, 32, s);
+    size_t b = tmp.bytes();
+    return rocprim::radix_sort_pairs(tmp.get(), b, keys_in, keys_out, vals_in, vals_out, n, 0, 32, s);
 }
 
 /* ---- statistics ------------------------------------------------------------------------------------------------------- */
@@ -384,19 +391,16 @@ static bool grad_spheres_ok(const float* sp, int n_spheres) {
 /* what both entries share: the rows of all existing voxels on the device and the order that sorts them by packed key */
 struct grad_rows {
     size_t n = 0;
-    gsdf_dev<unsigned long long> ukeys, skeys;
-    gsdf_dev<uint32_t> ubin, idx, order;
+    gsdf_dev<unsigned long long> ukeys;
+    gsdf_dev<uint32_t> ubin;
     gsdf_dev<float> urows;
-    gsdf_dev<void> tmp;
+    gsdf_key_order ord;
 };
 
 static int grad_count(gsdf_ctx* c, size_t* n) {
-    HIP_TRY(hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream));
-    gsdf_launch_export(c->stream, c->tab, c->n_slots, nullptr, nullptr, c->counter, 0, 0, nullptr, 0, nullptr);
-    unsigned long long h = 0;
-    HIP_TRY(hipMemcpyAsync(&h, c->counter, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (h > 2147483647ull) return gfail(GSDF_ERR_INVALID, "gradient analysis: more than 2^31 - 1 voxels (row indices are 32-bit)");
+    int64_t h = 0;
+    if (int rc = gsdf_count(c, &h)) return rc;
+    if (h > 2147483647ll) return gfail(GSDF_ERR_INVALID, "gradient analysis: more than 2^31 - 1 voxels (row indices are 32-bit)");
     *n = (size_t)h;
     return GSDF_OK;
 }
@@ -409,21 +413,16 @@ static int grad_compute_rows(gsdf_ctx* c, const float* spheres4_host, int n_sphe
     HIP_TRY(d_box.alloc(6));
     HIP_TRY(d_par.alloc(256 + 256));
     HIP_TRY(R.ukeys.alloc(n));
-    HIP_TRY(R.skeys.alloc(n));
     HIP_TRY(R.ubin.alloc(n));
-    HIP_TRY(R.idx.alloc(n));
-    HIP_TRY(R.order.alloc(n));
     HIP_TRY(R.urows.alloc(n * 5));
-    size_t b0 = 0;
-    HIP_TRY(gsdf_sort_pairs_u64(nullptr, &b0, R.ukeys, R.skeys, R.idx, R.order, n, c->stream));
-    HIP_TRY(R.tmp.alloc(std::max<size_t>(b0, 8)));
+    HIP_TRY(R.ord.alloc(n));
     float par[512] = { 0.f };
     std::copy(spheres4_host, spheres4_host + 4 * n_spheres, par);
     if (n_thr) std::copy(thresholds, thresholds + n_thr, par + 256);
     const int box[6] = { 2147483647, 2147483647, 2147483647, -2147483647 - 1, -2147483647 - 1, -2147483647 - 1 };
     HIP_TRY(hipMemcpyAsync(d_box, box, sizeof(box), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_par, par, sizeof(par), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream));
+    HIP_TRY(gsdf_counter_zero(c));
     const size_t n_blocks = (size_t)c->tab.block_mask + 1;
     const unsigned int grid = (unsigned int)std::min<size_t>((n_blocks + 3) / 4, 4096);
     hipLaunchKernelGGL(k_grad_bbox, dim3(std::min(grid, 1024u)), dim3(256), 0, c->stream, c->tab, n_blocks, d_box.get());
@@ -433,9 +432,7 @@ static int grad_compute_rows(gsdf_ctx* c, const float* spheres4_host, int n_sphe
     a.max_n = (long long)n;
     hipLaunchKernelGGL(k_grad_angles, dim3(grid), dim3(256), 0, c->stream, a);
     HIP_TRY(hipGetLastError());
-    gsdf_launch_iota(c->stream, R.idx, n);
-    b0 = R.tmp.bytes();
-    HIP_TRY(gsdf_sort_pairs_u64(R.tmp, &b0, R.ukeys, R.skeys, R.idx, R.order, n, c->stream));
+    HIP_TRY(R.ord.run(c, R.ukeys, n));
     /* d_box and d_par are released on return: hipFree waits for the kernels that read them (gsdf_dev.h) */
     return GSDF_OK;
 }
@@ -457,7 +454,7 @@ int gsdf_gradient_angles(gsdf_ctx* c, const float* spheres4_host, int n_spheres,
     gsdf_dev<float> d_rows;
     if (keys) HIP_TRY(d_keys3.alloc(R.n * 3));
     if (rows5) HIP_TRY(d_rows.alloc(R.n * 5));
-    hipLaunchKernelGGL(k_grad_gather, dim3((unsigned int)((R.n + 255) / 256)), dim3(256), 0, c->stream, R.skeys.get(), R.order.get(),
+    hipLaunchKernelGGL(k_grad_gather, dim3((unsigned int)((R.n + 255) / 256)), dim3(256), 0, c->stream, R.ord.skeys.get(), R.ord.order.get(),
                        R.urows.get(), R.ubin.get(), R.n, keys ? d_keys3.get() : nullptr, rows5 ? d_rows.get() : nullptr, (uint32_t*)nullptr,
                        (uint32_t*)nullptr);
     HIP_TRY(hipGetLastError());
@@ -467,7 +464,7 @@ int gsdf_gradient_angles(gsdf_ctx* c, const float* spheres4_host, int n_spheres,
     if (keys) HIP_TRY(hipMemcpyAsync(hk.data(), d_keys3, hk.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     if (rows5) HIP_TRY(hipMemcpyAsync(hr.data(), d_rows, hr.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     unsigned long long n2 = 0;
-    HIP_TRY(hipMemcpyAsync(&n2, c->counter, sizeof(n2), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(gsdf_counter_read(c, &n2));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (n2 != R.n) return gfail(GSDF_ERR_HIP, "gsdf_gradient_angles: the map changed between the counting and the angle pass");
     if (keys) std::copy(hk.begin(), hk.end(), keys);
@@ -509,15 +506,13 @@ int gsdf_gradient_stats(gsdf_ctx* c, const float* spheres4_host, int n_spheres, 
     HIP_TRY(d_sq.alloc(4 * n_chunks * n_thr));
     HIP_TRY(d_tot.alloc((size_t)4 * n_thr * 2));
     HIP_TRY(d_stats.alloc(n_out));
-    size_t b1 = 0;
-    HIP_TRY(grad_sort_pairs_u32(nullptr, &b1, d_phis, d_sphis, d_bins, d_sbins, n, c->stream));
-    HIP_TRY(d_tmp.alloc(std::max<size_t>(b1, 8)));
-    hipLaunchKernelGGL(k_grad_gather, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, c->stream, R.skeys.get(), R.order.get(),
+    size_t need = 0;
+    HIP_TRY(grad_sort_pairs_u32_need(n, &need));
+    HIP_TRY(d_tmp.alloc(need));
+    hipLaunchKernelGGL(k_grad_gather, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, c->stream, R.ord.skeys.get(), R.ord.order.get(),
                        R.urows.get(), R.ubin.get(), n, (int32_t*)nullptr, (float*)nullptr, d_phis.get(), d_bins.get());
-    for (size_t e = 0; e < 4; ++e) {
-        b1 = d_tmp.bytes();
-        HIP_TRY(grad_sort_pairs_u32(d_tmp, &b1, d_phis + e * n, d_sphis + e * n, d_bins, d_sbins + e * n, n, c->stream));
-    }
+    for (size_t e = 0; e < 4; ++e)
+        HIP_TRY(grad_sort_pairs_u32(d_tmp, d_phis + e * n, d_sphis + e * n, d_bins, d_sbins + e * n, n, c->stream));
     hipLaunchKernelGGL(k_grad_chunk_stats, dim3((unsigned int)n_chunks, 4), dim3(256), 0, c->stream, d_sphis.get(), d_sbins.get(), n, n_thr,
                        n_chunks, d_cnt.get(), d_sum.get(), d_sq.get());
     hipLaunchKernelGGL(k_grad_chunk_scan, dim3(1, 4), dim3(256), 0, c->stream, d_cnt.get(), d_sum.get(), d_sq.get(), n_thr, n_chunks, d_tot.get());
@@ -526,7 +521,7 @@ int gsdf_gradient_stats(gsdf_ctx* c, const float* spheres4_host, int n_spheres, 
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(hs.data(), d_stats, n_out * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     unsigned long long n2 = 0;
-    HIP_TRY(hipMemcpyAsync(&n2, c->counter, sizeof(n2), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(gsdf_counter_read(c, &n2));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (n2 != n) return gfail(GSDF_ERR_HIP, "gsdf_gradient_stats: the map changed between the counting and the angle pass");
     std::copy(hs.begin(), hs.end(), stats);

@@ -7,6 +7,8 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
+#include "gsdf_dev.h"
 #include "gsdf_table.h"
 
 #define GSDF_STATUS_TABLE_FULL 1
@@ -213,27 +215,42 @@ void gsdf_launch_raycast(hipStream_t s, gsdf_table tab, float vs, float inv_vs, 
 void gsdf_launch_mesh(hipStream_t s, gsdf_table tab, size_t n_slots, float vs, float iso, int* mn_dev, const signed char* tri_table_dev,
                       float* tris_dev, unsigned long long* keys_dev, unsigned long long* counter, long long max_tris);
 
-/* mesh export: device radix sort of (64-bit sweep key, triangle index) pairs (rocPRIM; tmp == nullptr: only *tmp_bytes is set),
- * index fill, and the gather of 9-float triangles into sorted order (gsdf_sort.hip) */
-hipError_t gsdf_sort_keys_u64(void* tmp, size_t* tmp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out, size_t n,
+/* The rocPRIM wrappers come in pairs.  X_need(n, &need) launches nothing and RAISES *need to the scratch X wants for n items, at
+ * least 8 bytes (it never lowers *need: prims that share one scratch are sized by consecutive calls on one variable).  X(tmp, ...)
+ * runs with tmp.get() and tmp.bytes(); a scratch that is too small is rocPRIM's own error (hipErrorInvalidValue). */
+template <class Query /* hipError_t(size_t& bytes): the prim called with a null scratch */>
+hipError_t gsdf_scratch_need(size_t* need, Query&& query) {
+    size_t b = 0;
+    const hipError_t e = query(b);
+    if (e == hipSuccess) *need = std::max(*need, std::max<size_t>(b, 8));
+    return e;
+}
+
+/* mesh export: device radix sort of (64-bit sweep key, triangle index) pairs (rocPRIM), index fill, and the gather of 9-float
+ * triangles into sorted order (gsdf_sort.hip) */
+hipError_t gsdf_sort_keys_u64_need(size_t n, size_t* need);
+hipError_t gsdf_sort_keys_u64(const gsdf_dev<void>& tmp, const unsigned long long* keys_in, unsigned long long* keys_out, size_t n,
                               hipStream_t s);
-hipError_t gsdf_unique_u64(void* tmp, size_t* tmp_bytes, const unsigned long long* sorted_in, unsigned long long* out,
+hipError_t gsdf_unique_u64_need(size_t n, size_t* need);
+hipError_t gsdf_unique_u64(const gsdf_dev<void>& tmp, const unsigned long long* sorted_in, unsigned long long* out,
                            unsigned long long* count_out, size_t n, hipStream_t s);
-hipError_t gsdf_sort_pairs_u64(void* tmp, size_t* tmp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out,
+hipError_t gsdf_sort_pairs_u64_need(size_t n, size_t* need);
+hipError_t gsdf_sort_pairs_u64(const gsdf_dev<void>& tmp, const unsigned long long* keys_in, unsigned long long* keys_out,
                                const uint32_t* vals_in, uint32_t* vals_out, size_t n, hipStream_t s);
 void gsdf_launch_iota(hipStream_t s, uint32_t* idx, size_t n);
 void gsdf_launch_gather_tris(hipStream_t s, const float* tris, const uint32_t* order, float* sorted, size_t n);
 
 /* the indexed mesh (gsdf_mesh_index.hip): k_mesh's triangles with, per corner, the key of its grid edge (lower endpoint relative
  * to mn_dev, z-y-x at 20 bits each, then the axis in 2 bits) and a word of interpolate's mu | walked-downwards << 31; the edge
- * keys of the corners brought into sweep order with their ranks; run starts of the sorted keys and their exclusive scan (rocPRIM;
- * tmp == nullptr: only *tmp_bytes is set); faces / vertex positions / per-vertex key and mu word; the normals */
+ * keys of the corners brought into sweep order with their ranks; run starts of the sorted keys and their exclusive scan (rocPRIM);
+ * faces / vertex positions / per-vertex key and mu word; the normals */
 void gsdf_launch_mesh_corners(hipStream_t s, gsdf_table tab, size_t n_slots, float vs, float iso, const int* mn_dev,
                               const signed char* tri_table_dev, float* tris_dev, unsigned long long* keys_dev,
                               unsigned long long* ekeys_dev, uint32_t* muw_dev, unsigned long long* counter, long long max_tris);
 void gsdf_launch_corner_keys(hipStream_t s, const unsigned long long* ekeys, const uint32_t* order, unsigned long long* out,
                              uint32_t* rank, size_t n_tris);
-hipError_t gsdf_run_heads_scan(void* tmp, size_t* tmp_bytes, const unsigned long long* sorted, uint32_t* heads, uint32_t* before, size_t n,
+hipError_t gsdf_run_heads_scan_need(size_t n, size_t* need);
+hipError_t gsdf_run_heads_scan(const gsdf_dev<void>& tmp, const unsigned long long* sorted, uint32_t* heads, uint32_t* before, size_t n,
                                hipStream_t s);
 void gsdf_launch_weld(hipStream_t s, const unsigned long long* sorted, const uint32_t* rank, const uint32_t* heads, const uint32_t* before,
                       const uint32_t* order, const float* tris, const uint32_t* muw, size_t n_corners, int32_t* faces, float* vertices,
@@ -242,14 +259,15 @@ void gsdf_launch_vertex_normals(hipStream_t s, gsdf_table tab, const int* mn_dev
                                 size_t n_vertices, float* normals);
 
 /* connected components of the indexed mesh (gsdf_mesh_components.hip).  label: parent[v] = v, the lock-free union over the faces,
- * then root[v] and flags[v] = (root[v] == v); scan_u32: rocPRIM exclusive scan (tmp == nullptr: only *tmp_bytes is set); tables:
+ * then root[v] and flags[v] = (root[v] == v); scan_u32: rocPRIM exclusive scan; tables:
  * vcomp[v] = before[root[v]], fcomp[f], counts (faces, vertices per component; zeroed here) and, with box_bits != nullptr, the
  * bounding boxes (6 words of scratch and 6 floats per component); keep: the mask over the components for min_faces >= 1, or the
  * largest (lowest id among equals) for min_faces < 0, and *n_kept; keep_flags: flags[i] = keep[comp[i]]; compact: the kept
  * vertices and faces in their order, ids remapped through vbefore (nrm / n_out nullable together) */
 void gsdf_launch_cc_label(hipStream_t s, const int32_t* faces, size_t n_faces, size_t n_vertices, uint32_t* parent, uint32_t* root,
                           uint32_t* flags);
-hipError_t gsdf_scan_u32(void* tmp, size_t* tmp_bytes, const uint32_t* in, uint32_t* out, size_t n, hipStream_t s);
+hipError_t gsdf_scan_u32_need(size_t n, size_t* need);
+hipError_t gsdf_scan_u32(const gsdf_dev<void>& tmp, const uint32_t* in, uint32_t* out, size_t n, hipStream_t s);
 void gsdf_launch_cc_tables(hipStream_t s, const int32_t* faces, const float* vertices, const uint32_t* root, const uint32_t* before,
                            size_t n_faces, size_t n_vertices, size_t n_comp, int32_t* vcomp, int32_t* fcomp, int32_t* counts,
                            uint32_t* box_bits, float* box);
@@ -297,9 +315,9 @@ struct gsdf_ba_dev {
      * of repeating that loop (solvePose :520-560 computes exactly getEnergy's :287-311 unless the loss truncates) */
     void* mean_cache;
 };
-/* the list above: ordered compaction of the table's slots (rocPRIM select over a counting iterator; tmp == nullptr: only
- * *tmp_bytes is set) */
-hipError_t gsdf_ba_compact(hipStream_t s, const gsdf_ba_dev& d, uint32_t* list_out, unsigned long long* count_out, void* tmp, size_t* tmp_bytes);
+/* the list above: ordered compaction of the table's slots (rocPRIM select over a counting iterator) */
+hipError_t gsdf_ba_compact_need(const gsdf_ba_dev& d, size_t* need);
+hipError_t gsdf_ba_compact(const gsdf_dev<void>& tmp, hipStream_t s, const gsdf_ba_dev& d, uint32_t* list_out, unsigned long long* count_out);
 void gsdf_launch_ba_energy(hipStream_t s, const gsdf_ba_dev& d, double* block_E, bool write_mean_cache = false /* needs gate_list and mean_cache */);
 void gsdf_launch_ba_dist(hipStream_t s, const gsdf_ba_dev& d, float damping, double* block_cnt /* nullable: [2][gsdf_ba_blocks()] voxels, observations */);
 void gsdf_launch_ba_pose(hipStream_t s, const gsdf_ba_dev& d, float* block_part, float* out, bool use_mean_cache = false /* written by an energy sweep at this very state */);

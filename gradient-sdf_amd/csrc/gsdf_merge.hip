@@ -160,10 +160,10 @@ int mx_ensure(gsdf_ctx* c, int i, size_t bytes, bool spare) {
 int mx_ensure_sized(gsdf_ctx* c, size_t n_all) {
     for (int i : { MX_KEYS_ALL, MX_SORTED, MX_UNION })
         if (int rc = mx_ensure(c, i, n_all * sizeof(unsigned long long), false)) return rc;
-    size_t tmp_sort = 0, tmp_uniq = 0;
-    HIP_TRY(gsdf_sort_keys_u64(nullptr, &tmp_sort, nullptr, nullptr, n_all, c->stream));
-    HIP_TRY(gsdf_unique_u64(nullptr, &tmp_uniq, nullptr, nullptr, nullptr, n_all, c->stream));
-    return mx_ensure(c, MX_TMP, std::max(tmp_sort, tmp_uniq), false);
+    size_t need = 0;
+    HIP_TRY(gsdf_sort_keys_u64_need(n_all, &need));
+    HIP_TRY(gsdf_unique_u64_need(n_all, &need));
+    return mx_ensure(c, MX_TMP, need, false);
 }
 
 int read_status(gsdf_ctx* c) {
@@ -315,10 +315,8 @@ int merge_impl(gsdf_ctx* c, transport& tr, int64_t* n_blocks_out, int64_t* bytes
     unsigned long long* uk = c->mx[MX_UNION].as<unsigned long long>();
     rc = tr.allgather(c, c->tab.bkeys, keys_all, cap * sizeof(unsigned long long));
     if (rc) return rc;
-    size_t tmp_bytes = c->mx[MX_TMP].bytes();
-    HIP_TRY(gsdf_sort_keys_u64(c->mx[MX_TMP], &tmp_bytes, keys_all, sorted, n_all, c->stream));
-    tmp_bytes = c->mx[MX_TMP].bytes();
-    HIP_TRY(gsdf_unique_u64(c->mx[MX_TMP], &tmp_bytes, sorted, uk, c->counter, n_all, c->stream));
+    HIP_TRY(gsdf_sort_keys_u64(c->mx[MX_TMP], keys_all, sorted, n_all, c->stream));
+    HIP_TRY(gsdf_unique_u64(c->mx[MX_TMP], sorted, uk, c->counter, n_all, c->stream));
     hipLaunchKernelGGL(k_union_size, dim3(1), dim3(64), 0, c->stream, uk, c->counter);
     HIP_TRY(hipGetLastError());
     unsigned long long nu64 = 0;
@@ -627,10 +625,8 @@ int gsdf_merge_prepare(gsdf_ctx* c, int nranks) {
     unsigned long long* keys_all = c->mx[MX_KEYS_ALL].as<unsigned long long>();
     HIP_TRY(hipMemsetAsync(keys_all, 0xFF, n_all * sizeof(unsigned long long), c->stream));
     HIP_TRY(hipMemcpyAsync(keys_all, c->tab.bkeys, cap * sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
-    size_t tb = c->mx[MX_TMP].bytes();
-    HIP_TRY(gsdf_sort_keys_u64(c->mx[MX_TMP], &tb, keys_all, c->mx[MX_SORTED].as<unsigned long long>(), n_all, c->stream));
-    tb = c->mx[MX_TMP].bytes();
-    HIP_TRY(gsdf_unique_u64(c->mx[MX_TMP], &tb, c->mx[MX_SORTED].as<unsigned long long>(), c->mx[MX_UNION].as<unsigned long long>(), c->counter, n_all, c->stream));
+    HIP_TRY(gsdf_sort_keys_u64(c->mx[MX_TMP], keys_all, c->mx[MX_SORTED].as<unsigned long long>(), n_all, c->stream));
+    HIP_TRY(gsdf_unique_u64(c->mx[MX_TMP], c->mx[MX_SORTED].as<unsigned long long>(), c->mx[MX_UNION].as<unsigned long long>(), c->counter, n_all, c->stream));
     hipLaunchKernelGGL(k_union_size, dim3(1), dim3(64), 0, c->stream, c->mx[MX_UNION].as<unsigned long long>(), c->counter);
     unsigned long long n_mine = 0;
     HIP_TRY(hipMemcpyAsync(&n_mine, c->counter, sizeof(n_mine), hipMemcpyDeviceToHost, c->stream));

@@ -90,8 +90,12 @@ void gsdf_launch_cc_label(hipStream_t s, const int32_t* faces, size_t n_faces, s
     hipLaunchKernelGGL(k_cc_roots, gv, b, 0, s, parent, n_vertices, root, flags);
 }
 
-hipError_t gsdf_scan_u32(void* tmp, size_t* tmp_bytes, const uint32_t* in, uint32_t* out, size_t n, hipStream_t s) {
-    return rocprim::exclusive_scan(tmp, *tmp_bytes, in, out, 0u, n, rocprim::plus<uint32_t>(), s);
+hipError_t gsdf_scan_u32_need(size_t n, size_t* need) {
+    return gsdf_scratch_need(need, [n](size_t& b) { return rocprim::exclusive_scan(nullptr, b, (const uint32_t*)0, (uint32_t*)0, 0u, n, rocprim::plus<uint32_t>(), hipStream_t()); });
+}
+hipError_t gsdf_scan_u32(const gsdf_dev<void>& tmp, const uint32_t* in, uint32_t* out, size_t n, hipStream_t s) {
+    size_t b = tmp.bytes();
+    return rocprim::exclusive_scan(tmp.get(), b, in, out, 0u, n, rocprim::plus<uint32_t>(), s);
 }
 
 /* a float as an unsigned whose order is the float's (-0 below +0; a NaN sorts beyond the infinity of its sign) */

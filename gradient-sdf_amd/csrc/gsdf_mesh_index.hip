@@ -133,12 +133,15 @@ __global__ __launch_bounds__(256) void k_run_heads(const unsigned long long* __r
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) heads[i] = (i == 0 || sorted[i] != sorted[i - 1]) ? 1u : 0u;
 }
-/* heads[i] = corner i of the sorted list starts a run of equal keys; before[i] = run starts in front of i (tmp == nullptr:
- * only *tmp_bytes is set, nothing is launched) */
-hipError_t gsdf_run_heads_scan(void* tmp, size_t* tmp_bytes, const unsigned long long* sorted, uint32_t* heads, uint32_t* before, size_t n,
+/* heads[i] = corner i of the sorted list starts a run of equal keys; before[i] = run starts in front of i */
+hipError_t gsdf_run_heads_scan_need(size_t n, size_t* need) {
+    return gsdf_scratch_need(need, [n](size_t& b) { return rocprim::exclusive_scan(nullptr, b, (uint32_t*)0, (uint32_t*)0, 0u, n, rocprim::plus<uint32_t>(), hipStream_t()); });
+}
+hipError_t gsdf_run_heads_scan(const gsdf_dev<void>& tmp, const unsigned long long* sorted, uint32_t* heads, uint32_t* before, size_t n,
                                hipStream_t s) {
-    if (tmp && n) hipLaunchKernelGGL(k_run_heads, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, s, sorted, heads, n);
-    return rocprim::exclusive_scan(tmp, *tmp_bytes, heads, before, 0u, n, rocprim::plus<uint32_t>(), s);
+    if (n) hipLaunchKernelGGL(k_run_heads, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, s, sorted, heads, n);
+    size_t b = tmp.bytes();
+    return rocprim::exclusive_scan(tmp.get(), b, heads, before, 0u, n, rocprim::plus<uint32_t>(), s);
 }
 
 /* one lane per corner of the sorted list */

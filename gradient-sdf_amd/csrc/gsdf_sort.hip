@@ -13,19 +13,35 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_select.hpp>
 
-hipError_t gsdf_sort_pairs_u64(void* tmp, size_t* tmp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out,
+typedef unsigned long long u64;
+/* (the size queries name the run's pointer types: they must not instantiate a second set of rocPRIM's kernels) */
+hipError_t gsdf_sort_pairs_u64_need(size_t n, size_t* need) {
+    return gsdf_scratch_need(need, [n](size_t& b) {
+        return rocprim::radix_sort_pairs(nullptr, b, (const u64*)0, (u64*)0, (const uint32_t*)0, (uint32_t*)0, n, 0, 64, hipStream_t());
+    });
+}
+hipError_t gsdf_sort_pairs_u64(const gsdf_dev<void>& tmp, const unsigned long long* keys_in, unsigned long long* keys_out,
                                const uint32_t* vals_in, uint32_t* vals_out, size_t n, hipStream_t s) {
-    return rocprim::radix_sort_pairs(tmp, *tmp_bytes, keys_in, keys_out, vals_in, vals_out, n, 0, 64, s);
+    size_t b = tmp.bytes();
+    return rocprim::radix_sort_pairs(tmp.get(), b, keys_in, keys_out, vals_in, vals_out, n, 0, 64, s);
 }
 
 /* the exchange's union of block ids (gsdf_merge.hip): sort all ranks' key arrays, keep one of each */
-hipError_t gsdf_sort_keys_u64(void* tmp, size_t* tmp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out, size_t n,
-                              hipStream_t s) {
-    return rocprim::radix_sort_keys(tmp, *tmp_bytes, keys_in, keys_out, n, 0, 64, s);
+hipError_t gsdf_sort_keys_u64_need(size_t n, size_t* need) {
+    return gsdf_scratch_need(need, [n](size_t& b) { return rocprim::radix_sort_keys(nullptr, b, (const u64*)0, (u64*)0, n, 0, 64, hipStream_t()); });
 }
-hipError_t gsdf_unique_u64(void* tmp, size_t* tmp_bytes, const unsigned long long* sorted_in, unsigned long long* out,
+hipError_t gsdf_sort_keys_u64(const gsdf_dev<void>& tmp, const unsigned long long* keys_in, unsigned long long* keys_out, size_t n,
+                              hipStream_t s) {
+    size_t b = tmp.bytes();
+    return rocprim::radix_sort_keys(tmp.get(), b, keys_in, keys_out, n, 0, 64, s);
+}
+hipError_t gsdf_unique_u64_need(size_t n, size_t* need) {
+    return gsdf_scratch_need(need, [n](size_t& b) { return rocprim::unique(nullptr, b, (const u64*)0, (u64*)0, (u64*)0, n, rocprim::equal_to<u64>(), hipStream_t()); });
+}
+hipError_t gsdf_unique_u64(const gsdf_dev<void>& tmp, const unsigned long long* sorted_in, unsigned long long* out,
                            unsigned long long* count_out, size_t n, hipStream_t s) {
-    return rocprim::unique(tmp, *tmp_bytes, sorted_in, out, count_out, n, rocprim::equal_to<unsigned long long>(), s);
+    size_t b = tmp.bytes();
+    return rocprim::unique(tmp.get(), b, sorted_in, out, count_out, n, rocprim::equal_to<unsigned long long>(), s);
 }
 
 __global__ __launch_bounds__(256) void k_iota(uint32_t* idx, size_t n) {

@@ -217,7 +217,8 @@ def test_grow_failure_leaves_the_map(pkg, L, seq):
     g.close()
 
 
-@pytest.mark.parametrize("what", ["export", "query", "raycast", "extract_mesh"])
+@pytest.mark.parametrize("what", ["export", "query", "raycast", "extract_mesh", "extract_mesh_indexed", "mesh_components",
+                                  "extract_mesh_indexed_filtered", "surface_cloud", "gradient_angles", "gradient_stats"])
 def test_temporary_failure_leaves_nothing_behind(pkg, L, seq, what):
     g = _wrap(pkg, L, _create(L), seq)
     _fuse2(g, seq)
@@ -225,11 +226,21 @@ def test_temporary_failure_leaves_nothing_behind(pkg, L, seq, what):
     rng = np.random.default_rng(0)
     pts = (rng.uniform(-1, 1, (10000, 3)) * 0.5 + np.array([0, 0, 1.5])).astype(np.float32)
     assert pts.shape[0] * 8 * 4 > 256 * 1024                         # above GSDF_SCRATCH_BYTES: the call allocates
+    sph = np.asarray(seq.spheres, np.float32).reshape(-1, 4)          # the scene's own spheres (test_gpu_gradient_analysis.py)
+    thr = [0.011, 0.1]
     call = {"export": lambda: g.export(sorted=True), "query": lambda: g.query(pts),
-            "raycast": lambda: g.raycast(R, t), "extract_mesh": lambda: (g.extract_mesh(),)}[what]
+            "raycast": lambda: g.raycast(R, t), "extract_mesh": lambda: (g.extract_mesh(),),
+            "extract_mesh_indexed": lambda: g.extract_mesh_indexed(), "mesh_components": lambda: g.mesh_components(),
+            "extract_mesh_indexed_filtered": lambda: g.extract_mesh_indexed_filtered(2),
+            "surface_cloud": lambda: (g.surface_cloud(),), "gradient_angles": lambda: g.gradient_angles(sph),
+            "gradient_stats": lambda: (g.gradient_stats(sph, thr),)}[what]
     call()                                                            # (what the context keeps is allocated now)
     want, n = _counted(L, call)
     assert n >= 1 and want[0].shape[0] > 0, n
+    if what == "extract_mesh_indexed_filtered":
+        assert want[2].shape[0] > 0 and want[4] >= 1, want[3:]        # faces were kept, of at least one component
+    if what == "gradient_stats":
+        assert (want[0][:, -1, 0] > 0).all(), want[0][:, :, 0]        # every estimator counted voxels: the map is not empty
     print("MEASURED %s makes %d owned allocations" % (what, n))
     for k in range(1, n + 1):
         assert _code_with_failure(pkg, L, k, call) == ERR_HIP, k
