@@ -86,6 +86,9 @@ def load_test_lib():
     L.gsdf_debug_ba_delta.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.gsdf_debug_fail_alloc.restype = C.c_int           # process-wide: the nth owned allocation from now on fails once (0 disarms)
     L.gsdf_debug_fail_alloc.argtypes = [C.c_int]
+    # gsdf_posed_blocks as gsdf_merge_from_posed's candidate kernel uses it (no context, no device): pose7, vs, src block[3] -> dst blocks
+    L.gsdf_debug_posed_blocks.restype = C.c_int
+    L.gsdf_debug_posed_blocks.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
     return L
 
 
@@ -150,6 +153,8 @@ def load(path=None):
         "gsdf_set_auto_grow": (C.c_int, [vp, C.c_int]),
         "gsdf_capacity": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "gsdf_merge_from": (C.c_int, [vp, vp]),
+        "gsdf_merge_from_posed": (C.c_int, [vp, vp, fp, i64p, i64p]),
+        "gsdf_merge_posed_last": (C.c_int, [vp, i64p, fp]),
         "gsdf_create_shards": (C.c_int, [C.POINTER(vp), C.c_int, C.c_float, C.c_float, C.c_int, C.c_int]),
         "gsdf_merge_raw": (C.c_int, [vp, i32p, fp, C.c_int64]),
         "gsdf_export_raw_dev": (C.c_int, [vp, vp, vp, C.c_int64, i64p]),
@@ -217,7 +222,7 @@ ABI_SYMBOLS = [
     "gsdf_sync", "gsdf_get_stats", "gsdf_count", "gsdf_export", "gsdf_enable_vis", "gsdf_export_vis",
     "gsdf_ba_setup", "gsdf_ba_set_loss", "gsdf_ba_energy", "gsdf_ba_solve_pose", "gsdf_ba_solve_dist", "gsdf_ba_optimize", "gsdf_ba_get_poses", "gsdf_ba_counters",
     "gsdf_ba_pose_system", "gsdf_ba_solve_pose_full", "gsdf_ba_set_pose_step",
-    "gsdf_color_compute", "gsdf_color_export", "gsdf_color_cloud", "gsdf_color_counters", "gsdf_color_mesh", "gsdf_grow", "gsdf_set_auto_grow", "gsdf_capacity", "gsdf_merge_from", "gsdf_create_shards", "gsdf_merge_prepare",
+    "gsdf_color_compute", "gsdf_color_export", "gsdf_color_cloud", "gsdf_color_counters", "gsdf_color_mesh", "gsdf_grow", "gsdf_set_auto_grow", "gsdf_capacity", "gsdf_merge_from", "gsdf_merge_from_posed", "gsdf_merge_posed_last", "gsdf_create_shards", "gsdf_merge_prepare",
     "gsdf_merge_raw", "gsdf_export_raw_dev",
     "gsdf_merge_raw_dev", "gsdf_block_keys_dev", "gsdf_pack_blocks_dev", "gsdf_unpack_blocks_dev",
     "gsdf_merge_allreduce", "gsdf_merge_allreduce_with", "gsdf_rccl_unique_id", "gsdf_rccl_comm_init", "gsdf_rccl_comm_count",
@@ -620,6 +625,27 @@ class GradSdf:
     def merge_from(self, other):
         """self += other (another context on the same device): gsdf_merge_from."""
         self._chk(self.L.gsdf_merge_from(self.h, other.h))
+
+    def merge_from_posed(self, other, pose7):
+        """self += other resampled on this map's grid under pose7 (tx ty tz qx qy qz qw, other's frame -> this map's, as
+        align_points returns it): gsdf_merge_from_posed.  Returns (n_voxels, n_blocks) that received a contribution.  A
+        GsdfError of GSDF_ERR_KEY_RANGE carries them as .counts: the packable part was merged."""
+        p = _f32(pose7).reshape(7).copy()
+        nv, nb = C.c_int64(0), C.c_int64(0)
+        rc = self.L.gsdf_merge_from_posed(self.h, other.h, _fp(p), C.byref(nv), C.byref(nb))
+        if rc != GSDF_OK:
+            e = GsdfError(rc, self.L.gsdf_last_error().decode())
+            e.counts = (nv.value, nb.value)
+            raise e
+        return nv.value, nb.value
+
+    def merge_posed_last(self):
+        """gsdf_merge_posed_last: ((candidate blocks, after unique), ms [4] = candidates, sort + unique, sample, add) of the
+        last merge_from_posed into this context"""
+        cnt = (C.c_int64 * 2)()
+        ms = np.zeros(4, np.float32)
+        self._chk(self.L.gsdf_merge_posed_last(self.h, cnt, _fp(ms)))
+        return (cnt[0], cnt[1]), ms
 
     def export_raw_dev(self, keys_ptr, payload_ptr, max_n):
         """Unsorted (key, raw sums) compaction into device buffers (e.g. torch tensors' data_ptr())."""

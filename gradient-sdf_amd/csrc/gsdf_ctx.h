@@ -188,6 +188,13 @@ struct gsdf_color_state {
     void drop() { valid = false; n = 0; obs = 0; cloud_n = -1; }   /* forgets the snapshot, keeps the buffers (gsdf_reset) */
 };
 
+/* what the last gsdf_merge_from_posed into this context did (gsdf_merge_posed_last): candidate blocks before / after unique;
+ * event times of the candidate list's filling pass, sort + unique, k_posed_sample, k_posed_add (ms) */
+struct gsdf_posed_last {
+    long long candidates = 0, unique = 0;
+    float ms[4] = { 0.f, 0.f, 0.f, 0.f };
+};
+
 struct gsdf_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -237,6 +244,7 @@ struct gsdf_ctx {
     gsdf_dev<unsigned int> grow_scratch;           /* two device words of k_count_blocks */
     bool merged = false;                           /* gsdf_merge_allreduce has run: the map is the sum of all ranks (one-shot) */
     gsdf_dev<void> mx[GSDF_MX_BUFS];               /* scratch of the exchange (gsdf_merge.hip): grows, never shrinks */
+    gsdf_posed_last posed_last;                    /* gsdf_merge_from_posed with this context as dst (gsdf_merge_posed.hip) */
     /* PhotoBA (PhotometricOptimizer) */
     int ba_n = 0;
     float ba_reg = 10.f;

@@ -141,6 +141,10 @@ bool MapGradPixelSdf::surface_cloud(std::vector<float>& rows6) const {
     rows6.assign((size_t)n * 6, 0.f);
     return n == 0 || gsdf_surface_cloud(ctx_, rows6.data(), n, &n) == GSDF_OK;
 }
+bool MapGradPixelSdf::merge_from(const MapGradPixelSdf& other, const SE3& pose, int64_t* n_voxels, int64_t* n_blocks) {
+    /* the pose goes as the 7 floats SE3 holds, like RigidPointOptimizer::optimize_points hands its pose_ to gsdf_align_points */
+    return gsdf_merge_from_posed(ctx_, other.ctx_, pose.pose7(), n_voxels, n_blocks) == GSDF_OK;
+}
 bool MapGradPixelSdf::save_sdf(std::string filename) { return gsdf_exports::write_sdf_txt(ctx_, voxel_size_, filename); }
 bool MapGradPixelSdf::extract_mesh(std::string filename) { return gsdf_exports::write_mesh_ply(ctx_, voxel_size_, filename, nullptr); }
 bool MapGradPixelSdf::extract_mesh_indexed(std::string filename) { return gsdf_exports::write_indexed_mesh_ply(ctx_, filename, nullptr, nullptr); }

@@ -57,6 +57,12 @@ public:
     /* extract_pc's rows (MapGradPixelSdf.cpp:182-195) in memory: x y z nx ny nz per row, (z, y, x) key order (gsdf_surface_cloud);
      * false on a MapPixelSdf or an error (gsdf_last_error) */
     bool surface_cloud(std::vector<float>& rows6) const;
+    /* this += other resampled on this map's grid under `pose` (other's frame -> this map's: what
+     * RigidPointOptimizer::optimize_points leaves in pose() after registering other's surface_cloud against this map):
+     * gsdf_merge_from_posed, not in the reference.  Nullable: voxels that received a contribution, blocks they lie in.  false
+     * when the library refuses (a MapPixelSdf on either side, enable_vis, different voxel size or truncation, no room) or reports
+     * keys beyond the packable range (the rest is merged then); gsdf_last_error says which */
+    bool merge_from(const MapGradPixelSdf& other, const SE3& pose, int64_t* n_voxels = nullptr, int64_t* n_blocks = nullptr);
     bool save_sdf(std::string filename) override;                      /* MapGradPixelSdf.cpp:222-296 */
     bool extract_mesh(std::string filename) override;                  /* MapGradPixelSdf.cpp:124-175 */
     /* the same surface as an indexed mesh with a gradient normal per vertex, binary PLY (gsdf_extract_mesh_indexed; not in the

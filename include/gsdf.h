@@ -356,6 +356,54 @@ int gsdf_merge_raw(gsdf_ctx* c, const int32_t* keys, const float* payload_raw, i
  * returns GSDF_ERR_TABLE_FULL with dst UNCHANGED.  Should the kernel itself still report a full table, dst holds part of src,
  * Sdf::counter_ is not advanced and dst is to be reset (gsdf_reset). */
 int gsdf_merge_from(gsdf_ctx* dst, gsdf_ctx* src);
+
+/* dst += src RESAMPLED on dst's voxel grid under a rigid pose: the step behind gsdf_surface_cloud + gsdf_align_points, for two
+ * maps that were NOT fused in one frame (a second session, a map of another run, a tracked shard).  The reference has one map
+ * and one session and no such function; like the raycaster this is defined on top of Sdf::weights / Sdf::tsdf
+ * (MapGradPixelSdf.h:109-125).
+ * pose7 = tx ty tz qx qy qz qw, src frame -> dst frame, exactly what gsdf_align_points leaves in its pose7.
+ * R = Eigen's toRotationMatrix of (qx qy qz qw) as it comes, NOT renormalised (the bits of the tracker's R); t = pose7[0..3);
+ * vs the common voxel size, T the common truncation distance.  For every voxel index K = (i, j, k) of dst's grid inside the
+ * packable key range, in float, without FMA, in this order:
+ *   1. c = (vs * (float)i, vs * (float)j, vs * (float)k)                       vox2float
+ *   2. d = c - t, per component
+ *   3. q = R^T d, each component x0 + (x1 + x2): q.x = R00 d.x + (R10 d.y + R20 d.z), ...
+ *   4. a component of q that is not finite: K gets nothing (tested before any float -> int conversion)
+ *   5. (w, phi) = what gsdf_query returns at q: weights() and tsdf() of the voxel V = float2vox(q) of src, phi = dist_V +
+ *      1.2 g^_V . (c_V - q) rounded once from double; w == 0 (V missing, beyond the key range, weight 0): K gets nothing
+ *   6. otherwise, with (S_w, S_s, S_gx, S_gy, S_gz) the stored sums of V, K receives
+ *        w' = S_w,   s' = S_w * truncate(phi, T) (one float product),   g' = R (S_gx, S_gy, S_gz), rows as x0 + (x1 + x2)
+ *   7. dst's sums at K become (w + w', s + s', g + g'), one float addition per field; a missing voxel or block counts as
+ *      zeros and is created.
+ * phi is tsdf() with its factor 1.2 and not a plain Taylor step because that IS the map's value off a voxel centre: tracker,
+ * raycaster, registration and extract_pc share it, so a surface point of the merged map lies where src's own extract_pc puts
+ * it, moved by the pose.  The raw gradient sum is rotated, not w g^: it keeps the magnitude gsdf_merge_from keeps and is linear.
+ * The clamp keeps |dist| <= T in dst.  With the identity pose the result differs from gsdf_merge_from's only in s, by the
+ * round trip S_w * (S_s / S_w).
+ * The result is a function of (dst, src, pose) alone: a key gets at most one contribution, there are no floating-point
+ * atomics and no order left to the scheduler; the same call on the same state gives the same bytes, also across gsdf_grow
+ * of either context.
+ * Sdf::counter_ of dst becomes the frames of both.  *n_voxels (nullable) = keys that received a contribution, *n_blocks
+ * (nullable) = dst blocks they lie in; both are 0 on every refusal.  Synchronous; a waiting pipelined fusion of either context is launched
+ * first; src is only read.
+ * GSDF_ERR_INVALID, nothing touched: a NULL context or pose, dst == src, different devices, different voxel size or
+ * truncation, either context of type GSDF_MAP_BASE (no stored gradient), either context with gsdf_enable_vis on (carrying the
+ * vis_ bit-vectors across a resampling is not built, and with it PhotoBA on a posed-merged map), a pose entry that is not
+ * finite, | qx^2 + qy^2 + qz^2 + qw^2 - 1 | > 1e-4.
+ * GSDF_ERR_TABLE_FULL, nothing touched: src's status holds a full table (as gsdf_merge_from).
+ * Room: the number B of dst blocks that receive something is known exactly before dst is written.  If blocks(dst) + B passes
+ * 45 % of dst's block entries dst is doubled first when gsdf_set_auto_grow allows it; if it would pass 90 % of them the call
+ * returns GSDF_ERR_TABLE_FULL with dst UNCHANGED.  A failed allocation (GSDF_ERR_HIP) leaves dst unchanged as well.  Scratch:
+ * 1280 B per candidate block of dst (about twice the blocks that receive).
+ * GSDF_ERR_KEY_RANGE: a key beyond the packable +-2^20 range would have received a contribution (evaluated up to +-2^22
+ * voxels; an image farther out counts as such).  Those keys are left out, the rest IS merged and counted, Sdf::counter_
+ * advances -- as gsdf_update reports samples it dropped. */
+int gsdf_merge_from_posed(gsdf_ctx* dst, gsdf_ctx* src, const float pose7[7],
+                          int64_t* n_voxels /* nullable */, int64_t* n_blocks /* nullable */);
+/* What the last gsdf_merge_from_posed into dst did, for tools: counts[2] = candidate blocks before / after de-duplication;
+ * ms[4] = event times of the candidate list's filling pass, sort + unique, the sampling kernel, the adding kernel.  Either may
+ * be NULL; zeros before the first call and for stages that did not run. */
+int gsdf_merge_posed_last(gsdf_ctx* dst, int64_t counts[2], float ms[4]);
 /* n (1..4) contexts for n frame shards on ONE device, like gsdf_create each -- but their streams are guaranteed to sit in n
  * different hardware queues (created at the device's highest stream priority: the runtime pools its queues per priority, and
  * nothing else uses that pool), so that their launches overlap.  Streams of the default priority share queues as soon as the
@@ -438,7 +486,8 @@ int gsdf_get_voxels(gsdf_ctx* c, const int32_t* keys_host, int64_t n, float* pay
 /* REGISTRATION OF A POINT SET against the map -- the loop of RigidPointOptimizer::optimize_sampled
  * (RigidPointOptimizer.cpp:51-96) over n points the caller brings instead of the back-projected pixels of :62-69: from :70 on
  * the reference's tracker never looks at the depth image again.  A second session's cloud, a LiDAR sweep, the vertices of a CAD
- * part: anything that is to be brought into the map's frame (e.g. in front of gsdf_merge_from, which needs both maps in one).
+ * part: anything that is to be brought into the map's frame (e.g. in front of gsdf_merge_from_posed, which takes the pose found here; gsdf_merge_from needs both
+ * maps in one frame).
  * pts: n rows x y z (float32) in the source frame; every coordinate must be finite.  pose7 in/out (tx ty tz qx qy qz qw, unit
  * quaternion): source -> map.  The context's persistent pose (gsdf_set_pose / gsdf_get_pose), the frame log and gsdf_stats are
  * neither read nor written.

@@ -6,7 +6,8 @@ B's surface cloud on the device (gsdf_surface_cloud_dev), moves it into a source
 (0.01, -0.008, 0.006) m, and registers it against A from the identity (gsdf_align_points_dev).  Reports points, hits, passes, the
 final E / hits, the recovered pose's error, the wall time of the call (median of `--reps` after one warm call), and the HIP-event
 time of one batch of 5 pass + head pairs divided by 5 (conv_threshold = 0, so all five run) next to the event time of
-k_track_pass's launches on map A for a frame of the stream.  One JSON line, also written to profiles/align_points.json (or --out)."""
+k_track_pass's launches on map A for a frame of the stream.  One JSON line, also written to profiles/align_points.json (or --out).
+--merge goes on to the merge under the recovered pose instead (merge_main): profiles/merge_posed.json."""
 import argparse, json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,12 +29,99 @@ def R_to_quat(R):
     return np.array([(R[2, 1] - R[1, 2]) / (4 * w), (R[0, 2] - R[2, 0]) / (4 * w), (R[1, 0] - R[0, 1]) / (4 * w), w], np.float32)
 
 
+def merge_main(args):
+    """--merge: B is fused in a frame of its OWN (every pose of its half premultiplied by the inverse of the displacement), its
+    cloud registered against A as it is, and B merged into a copy of A under the recovered pose and under the true one
+    (gsdf_merge_from_posed).  Reports the counts, the candidate blocks before / after unique, the wall time of the call (median of
+    --reps, each into a fresh copy of A), the event times of its stages, the wall time of gsdf_merge_from on the same two maps for
+    scale, and the median / 95th percentile of |phi| that A alone and the two merged maps return at the surface-cloud points of a
+    map fused from ALL frames at their ground-truth poses.  One JSON line, also written to profiles/merge_posed.json (or --out)."""
+    import __graft_entry__ as graft
+    import align_points_ref as ref
+    pkg = graft.package()
+    W, H, n = 640, 480, args.frames
+    seq = pkg.synth.Sequence("tum", W, H, n_frames=n, seed=0)
+    vs = np.float32(0.01); T = np.float32(10) * vs
+    new = lambda: pkg.GradSdf(vs, T, W, H, seq.K, capacity_log2=22)
+    a, b, full = new(), new(), new()
+    frames = [seq.frame(i) for i in range(n)]
+    _, Rd, td = ref.displace(np.zeros((1, 3)))
+    for i in range(n):
+        d, R, t = frames[i]
+        full.update(d, R, t)
+        if i < n // 2:
+            a.update(d, R, t)
+        else:                                           # B's own frame: x_b = Rd^T (x - td)
+            b.update(d, (Rd.T @ np.asarray(R, np.float64).reshape(3, 3)).astype(np.float32), (Rd.T @ (np.asarray(t, np.float64) - td)).astype(np.float32))
+    cloud_b = b.surface_cloud()
+    conv, pose, passes, trace = a.align_points(cloud_b[:, :3], ref.IDENTITY)
+    true = np.concatenate([td.astype(np.float32), R_to_quat(Rd)]).astype(np.float32)
+    Rg = quat_to_R(pose[3:])
+    ang = float(np.rad2deg(np.arccos(np.clip((np.trace(Rg.T @ Rd) - 1) / 2, -1, 1))))
+    terr = float(np.abs(pose[:3].astype(np.float64) - td).max())
+    probe = full.surface_cloud()[:, :3]
+
+    hit_a = a.query(probe)[2] > 0
+
+    def phi_stats(g):
+        """over the points the map answers, and over those of them that A alone answers too (the same set for every map)"""
+        phi, _, w = g.query(probe)
+        out = {}
+        for name, hit in (("", w > 0), ("_where_a_hits", (w > 0) & hit_a)):
+            v = np.abs(phi[hit].astype(np.float64))
+            out.update({"points_hit" + name: int(hit.sum()), "median_mm" + name: round(1e3 * float(np.median(v)), 4),
+                        "p95_mm" + name: round(1e3 * float(np.percentile(v, 95)), 4)})
+        return out
+
+    def copy_of_a():
+        g = new()
+        g.merge_from(a)
+        return g
+    res = {}
+    for name, p in (("true_pose", true), ("recovered_pose", pose)):
+        g = copy_of_a()
+        nv, nb = g.merge_from_posed(b, p)
+        (cand, uniq), ms = g.merge_posed_last()
+        res[name] = {"n_voxels": nv, "n_blocks": nb, "candidate_blocks": int(cand), "candidate_blocks_unique": int(uniq),
+                     "event_ms": {"candidates_fill": round(float(ms[0]), 4), "sort_unique": round(float(ms[1]), 4),
+                                  "k_posed_sample": round(float(ms[2]), 4), "k_posed_add": round(float(ms[3]), 4)},
+                     "voxels_after": g.count(), "abs_phi_at_full_map_cloud": phi_stats(g)}
+        g.close()
+    ts, tm = [], []
+    for _ in range(args.reps + 1):                      # the first one warm
+        g = copy_of_a()
+        t0 = time.perf_counter(); g.merge_from_posed(b, pose); ts.append(time.perf_counter() - t0)
+        g.close()
+        g = copy_of_a()
+        t0 = time.perf_counter(); g.merge_from(b); tm.append(time.perf_counter() - t0)
+        g.close()
+    out = {"map": "S-tum %dx%d, %d frames (A = first half, B = second half in a frame of its own), voxel %.3g m" % (W, H, n, float(vs)),
+           "voxels_a": a.count(), "voxels_b": b.count(), "blocks_b": int(len(np.unique(b.export()[0] >> 2, axis=0))),
+           "registration": {"points": int(len(cloud_b)), "converged": bool(conv), "passes": int(passes),
+                            "rotation_error_deg": round(ang, 4), "translation_error_mm": round(1e3 * terr, 3)},
+           "merge": res, "reps": args.reps,
+           "merge_from_posed_wall_ms": round(float(np.median(ts[1:])) * 1e3, 3),
+           "merge_from_wall_ms_same_maps_for_scale": round(float(np.median(tm[1:])) * 1e3, 3),
+           "abs_phi_at_full_map_cloud_a_alone": phi_stats(a), "full_map_cloud_points": int(len(probe))}
+    a.close(); b.close(); full.close()
+    line = json.dumps(out)
+    print(line)
+    with open(args.out, "w") as f:
+        f.write(line + "\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "align_points.json"))
+    ap.add_argument("--merge", action="store_true", help="also merge B into A under the recovered pose (gsdf_merge_from_posed); writes profiles/merge_posed.json")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "merge_posed.json" if args.merge else "align_points.json")
+    if args.merge:
+        return merge_main(args)
     import __graft_entry__ as graft
     import align_points_ref as ref
     pkg = graft.package()
