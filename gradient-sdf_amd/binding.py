@@ -163,6 +163,10 @@ def load(path=None):
         "gsdf_get_voxels": (C.c_int, [vp, i32p, C.c_int64, fp, i32p]),
         "gsdf_align_points": (C.c_int, [vp, fp, C.c_int64, fp, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int), fp]),
         "gsdf_align_points_dev": (C.c_int, [vp, vp, C.c_int64, fp, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int), fp]),
+        "gsdf_align_points_multi": (C.c_int, [vp, fp, C.c_int64, fp, C.c_int, C.c_int, C.c_float, C.c_float, i32p, i32p, fp, fp]),
+        "gsdf_align_points_multi_dev": (C.c_int, [vp, vp, C.c_int64, fp, C.c_int, C.c_int, C.c_float, C.c_float, i32p, i32p, fp, fp]),
+        "gsdf_align_starts": (C.c_int, [fp, fp, C.c_float, C.c_int, C.c_float, C.c_int, fp, C.c_int, C.POINTER(C.c_int)]),
+        "gsdf_align_best": (C.c_int, [C.c_int, i32p, i32p, fp, C.c_int64, C.c_int, C.POINTER(C.c_int)]),
         "gsdf_surface_cloud": (C.c_int, [vp, fp, C.c_int64, i64p]),
         "gsdf_surface_cloud_dev": (C.c_int, [vp, vp, C.c_int64, i64p]),
         "gsdf_block_keys_dev": (C.c_int, [vp, vp, C.c_int64, C.POINTER(C.c_int64)]),
@@ -228,6 +232,7 @@ ABI_SYMBOLS = [
     "gsdf_merge_allreduce", "gsdf_merge_allreduce_with", "gsdf_rccl_unique_id", "gsdf_rccl_comm_init", "gsdf_rccl_comm_count",
     "gsdf_rccl_comm_destroy",
     "gsdf_query", "gsdf_get_voxels", "gsdf_align_points", "gsdf_align_points_dev", "gsdf_surface_cloud", "gsdf_surface_cloud_dev",
+    "gsdf_align_points_multi", "gsdf_align_points_multi_dev", "gsdf_align_starts", "gsdf_align_best",
     "gsdf_raycast", "gsdf_raycast_dev", "gsdf_raycast_counters", "gsdf_extract_mesh",
     "gsdf_extract_mesh_indexed", "gsdf_mesh_components", "gsdf_extract_mesh_indexed_filtered", "gsdf_gradient_angles", "gsdf_gradient_stats",
     "gsdf_dev_alloc", "gsdf_dev_free", "gsdf_dev_upload", "gsdf_dev_download", "gsdf_timer_start", "gsdf_timer_stop_ms",
@@ -276,6 +281,41 @@ def _f32(a):
 
 def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def align_starts(center7, pivot, rot_step=0.0, rot_k=0, trans_step=0.0, trans_k=0, lib=None):
+    """gsdf_align_starts (host only): the (2 rot_k + 1)^3 (2 trans_k + 1)^3 starting poses [m, 7] around `center7`: rotation
+    vectors on the rot_step grid (radians) about `pivot` (source frame, e.g. the cloud's centroid), offsets on the trans_step
+    grid in the map frame; the middle row is the centre."""
+    L = load() if lib is None else lib
+    c, pv = _f32(center7).reshape(7), _f32(pivot).reshape(3)
+    m = C.c_int(0)
+    args = (_fp(c), _fp(pv), np.float32(rot_step), int(rot_k), np.float32(trans_step), int(trans_k))
+    rc = L.gsdf_align_starts(*args, None, 0, C.byref(m))
+    if rc != GSDF_OK:
+        raise GsdfError(rc, L.gsdf_last_error().decode())
+    out = np.zeros((m.value, 7), np.float32)
+    rc = L.gsdf_align_starts(*args, _fp(out), m.value, C.byref(m))
+    if rc != GSDF_OK:
+        raise GsdfError(rc, L.gsdf_last_error().decode())
+    return out
+
+
+def align_best(converged, passes, last, min_count=1, require_converged=True, lib=None):
+    """gsdf_align_best (host only): the index of the run with the smallest E / count among those that executed a pass, converged
+    (if required) and hit at least min_count points, or -1"""
+    L = load() if lib is None else lib
+    fl = np.ascontiguousarray(converged, dtype=np.int32).reshape(-1)
+    ps = np.ascontiguousarray(passes, dtype=np.int32).reshape(-1)
+    la = _f32(last).reshape(-1, 36)
+    if not (len(fl) == len(ps) == len(la)):
+        raise ValueError("align_best: converged, passes and last differ in length")
+    i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))                 # noqa: E731
+    best = C.c_int(-2)
+    rc = L.gsdf_align_best(len(fl), i32(fl), i32(ps), _fp(la), int(min_count), int(bool(require_converged)), C.byref(best))
+    if rc != GSDF_OK:
+        raise GsdfError(rc, L.gsdf_last_error().decode())
+    return best.value
 
 
 class GradSdf:
@@ -748,8 +788,31 @@ class GradSdf:
         p = pts_dev if isinstance(pts_dev, C.c_void_p) or pts_dev is None else C.c_void_p(int(pts_dev))
         return self._align(self.L.gsdf_align_points_dev, p, n, pose7, iters, conv, damping)
 
+    def _align_multi(self, fn, pts_arg, n, poses7, iters, conv, damping):
+        p = _f32(poses7).reshape(-1, 7).copy()
+        m, iters = len(p), int(iters)
+        flags, passes = np.zeros(m, np.int32), np.zeros(m, np.int32)
+        last = np.zeros((m, 36), np.float32)
+        trace = np.zeros((m, max(iters, 1), 36), np.float32)
+        i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))             # noqa: E731
+        self._chk(fn(self.h, pts_arg, int(n), _fp(p), m, iters, np.float32(conv), np.float32(damping), i32(flags), i32(passes),
+                     _fp(last), _fp(trace)))
+        return flags.astype(bool), p, passes, last, trace[:, :max(iters, 0)]
+
+    def align_points_multi(self, pts, poses7, iters=25, conv=1e-3, damping=1.0):
+        """gsdf_align_points_multi: align_points from every row of `poses7` [m, 7] at once, each run equal in bytes to the single
+        call from that row.  Returns (converged [m], poses [m, 7], passes [m], last [m, 36], trace [m, iters, 36]); the trace
+        rows of run h beyond passes[h] are zero, last[h] is its last executed row.  Starts: align_starts; pick: align_best."""
+        x = _f32(pts).reshape(-1, 3)
+        return self._align_multi(self.L.gsdf_align_points_multi, _fp(x) if len(x) else None, len(x), poses7, iters, conv, damping)
+
+    def align_points_multi_dev(self, pts_dev, n, poses7, iters=25, conv=1e-3, damping=1.0):
+        """the same over n x 3 floats already in device memory, as align_points_dev"""
+        p = pts_dev if isinstance(pts_dev, C.c_void_p) or pts_dev is None else C.c_void_p(int(pts_dev))
+        return self._align_multi(self.L.gsdf_align_points_multi_dev, p, n, poses7, iters, conv, damping)
+
     def surface_cloud(self):
-        """gsdf_surface_cloud: MapGradPixelSdf::extract_pc's rows [n, 6] = x y z nx ny nz, in (z, y, x) key order"""
+        """gsdf_surface_cloud:MapGradPixelSdf::extract_pc's rows [n, 6] = x y z nx ny nz, in (z, y, x) key order"""
         n = C.c_int64(0)
         self._chk(self.L.gsdf_surface_cloud(self.h, None, 0, C.byref(n)))
         rows = np.empty((n.value, 6), np.float32)

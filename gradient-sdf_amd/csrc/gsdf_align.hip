@@ -2,6 +2,7 @@
  * gsdf_align.hip -- registration of a point set against the map, and the map's own surface cloud (gfx950).
  *
  *   k_align_pass / k_align_head   RigidPointOptimizer::optimize_sampled, :70-95, over n given points   RigidPointOptimizer.cpp:51-96
+ *   k_align_pass_multi / k_align_head_multi   the same two bodies for a batch of starting poses, one run each, side by side
  *   k_surface_flag / k_surface_rows   MapGradPixelSdf::extract_pc's rows, in memory                    MapGradPixelSdf.cpp:177-195
  *
  * The reference's tracker turns the depth image into points (:62-69) and never looks at the image again (:70-82); the pass
@@ -16,6 +17,9 @@
  * and each of the 29 double totals is rounded to float once.  The order is a function of n and of the launch geometry, which is
  * a function of n alone: the same call gives the same bytes.  No floating-point atomics; the kernel boundary between a pass and
  * its head is the only grid barrier, there is no hand-off between workgroups inside a launch.
+ * The _multi kernels run the same two bodies for several starting poses in one launch pair: workgroup (x, y) of the pass is
+ * workgroup x of run live[y], workgroup y of the head is that run's head, each run on its own state, partial rows and trace rows.
+ * Per run the order above holds unchanged, so a run's bytes are those of a single call from its start.
  *
  * Both kernels are gathers over a table that is cache-resident at the project's map sizes; nothing here is MFMA-shaped.
  * Wave = 64 lanes.
@@ -33,12 +37,11 @@ int gsdf_align_grid(long long n) {
     return (int)(b < 1 ? 1 : (b > GSDF_ALIGN_MAXBLK ? GSDF_ALIGN_MAXBLK : b));
 }
 
-/* One pass over the points: part[workgroup][32] = this workgroup's 29 sums (slots 29..31 zero). */
-__global__ __launch_bounds__(GSDF_ALIGN_BLOCK) void k_align_pass(gsdf_table tab, float vs, float inv_vs, const float* __restrict__ pts,
-                                                                 long long n, const gsdf_align_state* __restrict__ st,
-                                                                 double* __restrict__ part) {
-    if (st->done) return;                                                  /* queued beyond the end of the run */
-    __shared__ double rows[ALIGN_WAVES][GSDF_ALIGN_ROW];
+/* One pass over the points for one run: part[workgroup][32] = this workgroup's 29 sums (slots 29..31 zero).  The body of
+ * k_align_pass and of k_align_pass_multi: blockIdx.x / gridDim.x are the workgroup's index and count within the run. */
+__device__ __forceinline__ void align_pass_body(gsdf_table tab, float vs, float inv_vs, const float* __restrict__ pts, long long n,
+                                                const gsdf_align_state* __restrict__ st, double* __restrict__ part,
+                                                double (&rows)[ALIGN_WAVES][GSDF_ALIGN_ROW]) {
     float R[9];
     gsdf_quat_to_R(st->pose7 + 3, R);                                      /* :53 */
     const gsdf_v3 t = { st->pose7[0], st->pose7[1], st->pose7[2] };        /* :54 */
@@ -92,18 +95,34 @@ __global__ __launch_bounds__(GSDF_ALIGN_BLOCK) void k_align_pass(gsdf_table tab,
     }
 }
 
+__global__ __launch_bounds__(GSDF_ALIGN_BLOCK) void k_align_pass(gsdf_table tab, float vs, float inv_vs, const float* __restrict__ pts,
+                                                                 long long n, const gsdf_align_state* __restrict__ st,
+                                                                 double* __restrict__ part) {
+    if (st->done) return;                                                  /* queued beyond the end of the run */
+    __shared__ double rows[ALIGN_WAVES][GSDF_ALIGN_ROW];
+    align_pass_body(tab, vs, inv_vs, pts, n, st, part, rows);
+}
+
+/* The same pass for the live runs of a batch of starts: workgroup (x, y) is workgroup x of run live[y].  st[m], part[m][gridDim.x][32]. */
+__global__ __launch_bounds__(GSDF_ALIGN_BLOCK) void k_align_pass_multi(gsdf_table tab, float vs, float inv_vs, const float* __restrict__ pts,
+                                                                       long long n, const gsdf_align_state* __restrict__ st,
+                                                                       double* __restrict__ part, const int* __restrict__ live) {
+    const int h = live[blockIdx.y];
+    if (st[h].done) return;                                                /* ended inside this batch */
+    __shared__ double rows[ALIGN_WAVES][GSDF_ALIGN_ROW];
+    align_pass_body(tab, vs, inv_vs, pts, n, st + h, part + (size_t)h * gridDim.x * GSDF_ALIGN_ROW, rows);
+}
+
 /* The head of one pass (:86-95): totals, solve, stop test, pose update, trace row.  The partial rows are staged through LDS
  * ALIGN_HEAD_ROWS at a time by the whole workgroup (a lane that loads its value row by row waits for a round trip per row:
  * measured with 190 rows, a 25-pass call took 1.51 ms that way and takes 0.65 ms this way); lane v < 29 then adds value v of
  * the staged rows in index order. */
 #define ALIGN_HEAD_THREADS 256
 #define ALIGN_HEAD_ROWS 64
-__global__ __launch_bounds__(ALIGN_HEAD_THREADS) void k_align_head(gsdf_align_state* __restrict__ st, const double* __restrict__ part,
-                                                                   int grid, float conv_sq, float damping, int max_passes,
-                                                                   float* __restrict__ trace) {
-    if (st->done) return;
-    __shared__ double stage[ALIGN_HEAD_ROWS * GSDF_ALIGN_ROW];
-    __shared__ float tot[GSDF_ALIGN_ROW];
+/* the body of k_align_head and of k_align_head_multi; `last` (nullable, 36 floats) receives every executed pass's row in turn */
+__device__ __forceinline__ void align_head_body(gsdf_align_state* __restrict__ st, const double* __restrict__ part, int grid, float conv_sq,
+                                                float damping, int max_passes, float* __restrict__ trace, float* __restrict__ last,
+                                                double (&stage)[ALIGN_HEAD_ROWS * GSDF_ALIGN_ROW], float (&tot)[GSDF_ALIGN_ROW]) {
     double s = 0.0;
     for (int b0 = 0; b0 < grid; b0 += ALIGN_HEAD_ROWS) {
         const int nrow = min(ALIGN_HEAD_ROWS, grid - b0);
@@ -141,6 +160,13 @@ __global__ __launch_bounds__(ALIGN_HEAD_THREADS) void k_align_head(gsdf_align_st
         for (int i = 0; i < 6; ++i) tr[29 + i] = xi[i];
         tr[35] = nrm;
     }
+    if (last) {
+#pragma unroll
+        for (int i = 0; i < GSDF_TRACK_NSUM; ++i) last[i] = tot[i];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) last[29 + i] = xi[i];
+        last[35] = nrm;
+    }
     st->passes = k + 1;
     if (nrm < conv_sq) {                                                   /* :88-91: xi is NOT applied */
         st->converged = 1;
@@ -163,11 +189,44 @@ __global__ __launch_bounds__(ALIGN_HEAD_THREADS) void k_align_head(gsdf_align_st
     if (k + 1 >= max_passes) st->done = 1;                                 /* :98 return false */
 }
 
+__global__ __launch_bounds__(ALIGN_HEAD_THREADS) void k_align_head(gsdf_align_state* __restrict__ st, const double* __restrict__ part,
+                                                                   int grid, float conv_sq, float damping, int max_passes,
+                                                                   float* __restrict__ trace) {
+    if (st->done) return;
+    __shared__ double stage[ALIGN_HEAD_ROWS * GSDF_ALIGN_ROW];
+    __shared__ float tot[GSDF_ALIGN_ROW];
+    align_head_body(st, part, grid, conv_sq, damping, max_passes, trace, nullptr, stage, tot);
+}
+
+/* The heads of the live runs side by side: workgroup y is the head of run live[y] on its rows part[h][grid][32], its state, its
+ * trace rows trace[h][max_passes][36] (nullable) and its last row last[h][36] (nullable). */
+__global__ __launch_bounds__(ALIGN_HEAD_THREADS) void k_align_head_multi(gsdf_align_state* __restrict__ st, const double* __restrict__ part,
+                                                                         int grid, float conv_sq, float damping, int max_passes,
+                                                                         float* __restrict__ trace, float* __restrict__ last,
+                                                                         const int* __restrict__ live) {
+    const int h = live[blockIdx.x];
+    if (st[h].done) return;
+    __shared__ double stage[ALIGN_HEAD_ROWS * GSDF_ALIGN_ROW];
+    __shared__ float tot[GSDF_ALIGN_ROW];
+    align_head_body(st + h, part + (size_t)h * grid * GSDF_ALIGN_ROW, grid, conv_sq, damping, max_passes,
+                    trace ? trace + (size_t)h * max_passes * 36 : nullptr, last ? last + (size_t)h * 36 : nullptr, stage, tot);
+}
+
 void gsdf_launch_align_pass(hipStream_t s, gsdf_table tab, float vs, float inv_vs, const float* pts, long long n,
                             gsdf_align_state* st, double* part, float conv_sq, float damping, int max_passes, float* trace) {
     const int grid = gsdf_align_grid(n);
     hipLaunchKernelGGL(k_align_pass, dim3(grid), dim3(GSDF_ALIGN_BLOCK), 0, s, tab, vs, inv_vs, pts, n, st, part);
     hipLaunchKernelGGL(k_align_head, dim3(1), dim3(ALIGN_HEAD_THREADS), 0, s, st, part, grid, conv_sq, damping, max_passes, trace);
+}
+
+void gsdf_launch_align_pass_multi(hipStream_t s, gsdf_table tab, float vs, float inv_vs, const float* pts, long long n,
+                                  gsdf_align_state* st, double* part, const int* live, int n_live, float conv_sq, float damping,
+                                  int max_passes, float* trace, float* last) {
+    if (n_live < 1) return;
+    const int grid = gsdf_align_grid(n);
+    hipLaunchKernelGGL(k_align_pass_multi, dim3(grid, n_live), dim3(GSDF_ALIGN_BLOCK), 0, s, tab, vs, inv_vs, pts, n, st, part, live);
+    hipLaunchKernelGGL(k_align_head_multi, dim3(n_live), dim3(ALIGN_HEAD_THREADS), 0, s, st, part, grid, conv_sq, damping, max_passes,
+                       trace, last, live);
 }
 
 /* ------------------------------------------------------------------------------------------------

@@ -1661,6 +1661,184 @@ int gsdf_align_points(gsdf_ctx* c, const float* pts_host, int64_t n, float pose7
     return align_points_impl(c, d, n, pose7, num_iterations, conv_threshold, damping, converged, passes, trace36);
 }
 
+/* m runs of align_points_impl side by side.  Scratch in c->align: the m states, the list of live runs behind them (at byte
+ * 64 m), then from byte 256 m the partial rows part[m][grid][GSDF_ALIGN_ROW].  The batches are those of the single call; after
+ * each the host reads the m states and packs the runs that have not ended into the list of the next batch's launches. */
+static int align_multi_impl(gsdf_ctx* c, const float* pts_dev, int64_t n, float* poses7, int m, int num_iterations, float conv_threshold,
+                            float damping, int* converged, int* passes, float* last36, float* trace36) {
+    const int grid = gsdf_align_grid(n);
+    const size_t need = (size_t)m * (256 + (size_t)grid * GSDF_ALIGN_ROW * sizeof(double));
+    if (c->align.bytes() < need) {                                         /* a failed allocation leaves the old scratch in place */
+        gsdf_dev<void> bigger;
+        HIP_TRY(bigger.alloc(need));
+        c->align = std::move(bigger);
+    }
+    gsdf_align_state* d_st = c->align.as<gsdf_align_state>();
+    int* d_live = (int*)(c->align.as<char>() + (size_t)m * 64);
+    double* d_part = (double*)(c->align.as<char>() + (size_t)m * 256);
+    gsdf_dev<float> d_trace, d_last;
+    const size_t trace_n = (size_t)m * num_iterations * 36;
+    if (trace36) HIP_TRY(d_trace.alloc(trace_n));
+    if (last36) HIP_TRY(d_last.alloc((size_t)m * 36));
+    std::vector<gsdf_align_state> h((size_t)m);
+    std::vector<int> live((size_t)m);
+    for (int i = 0; i < m; ++i) {
+        std::memcpy(h[i].pose7, poses7 + 7 * i, sizeof(h[i].pose7));
+        h[i].done = 0; h[i].converged = 0; h[i].passes = 0;
+        live[i] = i;
+    }
+    HIP_TRY(hipMemcpyAsync(d_st, h.data(), (size_t)m * sizeof(gsdf_align_state), hipMemcpyHostToDevice, c->stream));
+    if (trace36) HIP_TRY(hipMemsetAsync(d_trace, 0, trace_n * sizeof(float), c->stream));       /* rows beyond a run's end stay zero */
+    if (last36) HIP_TRY(hipMemsetAsync(d_last, 0, (size_t)m * 36 * sizeof(float), c->stream));
+    const float conv_sq = conv_threshold * conv_threshold;                 /* RigidOptimizer.h:72 */
+    int queued = 0, n_live = m;
+    while (queued < num_iterations && n_live > 0) {
+        const int batch = std::min(num_iterations - queued, queued == 0 ? c->first_batch : c->next_batch);
+        HIP_TRY(hipMemcpyAsync(d_live, live.data(), (size_t)n_live * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        for (int k = 0; k < batch; ++k)
+            gsdf_launch_align_pass_multi(c->stream, c->tab, c->voxel_size, c->voxel_size_inv, pts_dev, n, d_st, d_part, d_live, n_live,
+                                         conv_sq, damping, num_iterations, d_trace, d_last);
+        HIP_TRY(hipGetLastError());
+        queued += batch;
+        HIP_TRY(hipMemcpyAsync(h.data(), d_st, (size_t)m * sizeof(gsdf_align_state), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        int kept = 0;
+        for (int i = 0; i < n_live; ++i)
+            if (!h[live[i]].done) live[kept++] = live[i];                 /* index order is kept; the order has no bearing on a run's bytes */
+        n_live = kept;
+    }
+    if (trace36) HIP_TRY(hipMemcpyAsync(trace36, d_trace, trace_n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (last36) HIP_TRY(hipMemcpyAsync(last36, d_last, (size_t)m * 36 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (trace36 || last36) HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < m; ++i) {
+        std::memcpy(poses7 + 7 * i, h[i].pose7, sizeof(h[i].pose7));
+        converged[i] = h[i].converged;
+        passes[i] = h[i].passes;
+    }
+    return GSDF_OK;
+}
+
+static int align_multi_check(gsdf_ctx* c, const float* pts, int64_t n, const float* poses7, int m, int num_iterations,
+                             const int* converged, const int* passes) {
+    if (int rc = align_points_check(c, pts, n, poses7, num_iterations, converged, passes)) return rc;
+    if (m < 1 || m > GSDF_ALIGN_MAX_STARTS) return fail(GSDF_ERR_INVALID, "gsdf_align_points_multi: m outside 1 .. GSDF_ALIGN_MAX_STARTS");
+    return GSDF_OK;
+}
+
+/* num_iterations == 0, per run as the single call: nothing executed */
+static int align_multi_none(int m, int* converged, int* passes, float* last36) {
+    std::fill(converged, converged + m, 0);
+    std::fill(passes, passes + m, 0);
+    if (last36) std::fill(last36, last36 + (size_t)m * 36, 0.f);
+    return GSDF_OK;
+}
+
+int gsdf_align_points_multi_dev(gsdf_ctx* c, const float* pts_dev, int64_t n, float* poses7, int m, int num_iterations,
+                                float conv_threshold, float damping, int* converged, int* passes, float* last36, float* trace36) {
+    GSDF_FLUSH(c);
+    if (int rc = align_multi_check(c, pts_dev, n, poses7, m, num_iterations, converged, passes)) return rc;
+    if (num_iterations == 0) return align_multi_none(m, converged, passes, last36);
+    HIP_TRY(hipSetDevice(c->device));
+    return align_multi_impl(c, pts_dev, n, poses7, m, num_iterations, conv_threshold, damping, converged, passes, last36, trace36);
+}
+
+int gsdf_align_points_multi(gsdf_ctx* c, const float* pts_host, int64_t n, float* poses7, int m, int num_iterations,
+                            float conv_threshold, float damping, int* converged, int* passes, float* last36, float* trace36) {
+    GSDF_FLUSH(c);
+    if (int rc = align_multi_check(c, pts_host, n, poses7, m, num_iterations, converged, passes)) return rc;
+    if (num_iterations == 0) return align_multi_none(m, converged, passes, last36);
+    HIP_TRY(hipSetDevice(c->device));
+    gsdf_dev<void> big;
+    float* d = nullptr;
+    if (int rc = batch_scratch(c, (size_t)n * 3 * sizeof(float), big, (void**)&d)) return rc;
+    if (n > 0) HIP_TRY(hipMemcpyAsync(d, pts_host, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    return align_multi_impl(c, d, n, poses7, m, num_iterations, conv_threshold, damping, converged, passes, last36, trace36);
+}
+
+/* host only: the grid of starting poses around a centre (include/gsdf.h states the arithmetic; all of it in double) */
+int gsdf_align_starts(const float center7[7], const float pivot[3], float rot_step_rad, int rot_k, float trans_step, int trans_k,
+                      float* poses7_out, int max_m, int* m) {
+    if (!center7 || !pivot || !m) return fail(GSDF_ERR_INVALID, "gsdf_align_starts: null argument");
+    if (rot_k < 0 || trans_k < 0 || max_m < 0) return fail(GSDF_ERR_INVALID, "gsdf_align_starts: negative rot_k, trans_k or max_m");
+    bool finite = std::isfinite(rot_step_rad) && std::isfinite(trans_step);
+    for (int i = 0; i < 7; ++i) finite = finite && std::isfinite(center7[i]);
+    for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(pivot[i]);
+    if (!finite) return fail(GSDF_ERR_INVALID, "gsdf_align_starts: an input is not finite");
+    const double cq[4] = { center7[3], center7[4], center7[5], center7[6] };
+    const double cn = std::sqrt(cq[0] * cq[0] + cq[1] * cq[1] + cq[2] * cq[2] + cq[3] * cq[3]);
+    if (!(std::fabs(cn - 1.0) <= 1e-4)) return fail(GSDF_ERR_INVALID, "gsdf_align_starts: the centre's quaternion is not of unit length");
+    const long long Rn = 2LL * rot_k + 1, Tn = 2LL * trans_k + 1;
+    /* Rn, Tn < 2^32: a product that would pass 2^31 - 1 is reported as that */
+    long long count = 1;
+    for (const long long f : { Rn, Rn, Rn, Tn, Tn, Tn }) count = std::min<long long>(count * f, 0x7fffffffLL);
+    const int total = (int)count;
+    *m = total;
+    if (total > GSDF_ALIGN_MAX_STARTS) return fail(GSDF_ERR_INVALID, "gsdf_align_starts: more than GSDF_ALIGN_MAX_STARTS starts");
+    if (!poses7_out || max_m == 0) return GSDF_OK;                          /* the sizing call */
+    if (max_m < total) return fail(GSDF_ERR_INVALID, "gsdf_align_starts: max_m too small (*m holds the need)");
+    auto quat_R = [](const double q[4], double R[9]) {                      /* x y z w, unit length */
+        const double x = q[0], y = q[1], z = q[2], w = q[3];
+        R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w);     R[2] = 2 * (x * z + y * w);
+        R[3] = 2 * (x * y + z * w);     R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
+        R[6] = 2 * (x * z - y * w);     R[7] = 2 * (y * z + x * w);     R[8] = 1 - 2 * (x * x + y * y);
+    };
+    auto matvec = [](const double R[9], const double v[3], double o[3]) {
+        for (int i = 0; i < 3; ++i) o[i] = R[3 * i] * v[0] + R[3 * i + 1] * v[1] + R[3 * i + 2] * v[2];
+    };
+    const double qc[4] = { cq[0] / cn, cq[1] / cn, cq[2] / cn, cq[3] / cn };
+    const double tc[3] = { center7[0], center7[1], center7[2] }, pv[3] = { pivot[0], pivot[1], pivot[2] };
+    const double rs = rot_step_rad, ts = trans_step;
+    double Rc[9];
+    quat_R(qc, Rc);
+    int h = 0;
+    for (int a = 0; a < Rn; ++a) for (int b = 0; b < Rn; ++b) for (int cc = 0; cc < Rn; ++cc) {
+        const double r[3] = { rs * (a - rot_k), rs * (b - rot_k), rs * (cc - rot_k) };
+        const double th = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+        double qd[4] = { 0, 0, 0, 1 };
+        if (th > 0) {
+            const double s = std::sin(0.5 * th) / th;
+            qd[0] = s * r[0]; qd[1] = s * r[1]; qd[2] = s * r[2]; qd[3] = std::cos(0.5 * th);
+        }
+        /* q = qc (x) qd, Hamilton product */
+        double q[4] = { qc[3] * qd[0] + qc[0] * qd[3] + qc[1] * qd[2] - qc[2] * qd[1],
+                        qc[3] * qd[1] - qc[0] * qd[2] + qc[1] * qd[3] + qc[2] * qd[0],
+                        qc[3] * qd[2] + qc[0] * qd[1] - qc[1] * qd[0] + qc[2] * qd[3],
+                        qc[3] * qd[3] - qc[0] * qd[0] - qc[1] * qd[1] - qc[2] * qd[2] };
+        const double qn = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+        const double sg = q[3] < 0 ? -1.0 : 1.0;
+        for (int i = 0; i < 4; ++i) q[i] = sg * (q[i] / qn);
+        double Rd[9], dp[3], u[3], base[3];
+        quat_R(qd, Rd);
+        matvec(Rd, pv, dp);
+        for (int i = 0; i < 3; ++i) u[i] = pv[i] - dp[i];
+        matvec(Rc, u, base);
+        for (int d = 0; d < Tn; ++d) for (int e = 0; e < Tn; ++e) for (int f = 0; f < Tn; ++f, ++h) {
+            const double o[3] = { ts * (d - trans_k), ts * (e - trans_k), ts * (f - trans_k) };
+            float* out = poses7_out + 7 * (size_t)h;
+            for (int i = 0; i < 3; ++i) out[i] = (float)(base[i] + tc[i] + o[i]);
+            for (int i = 0; i < 4; ++i) out[3 + i] = (float)q[i];
+        }
+    }
+    return GSDF_OK;
+}
+
+/* host only: the run with the smallest E / count among the eligible ones */
+int gsdf_align_best(int m, const int* converged, const int* passes, const float* last36, int64_t min_count, int require_converged,
+                    int* best) {
+    if (m < 1 || !converged || !passes || !last36 || !best) return fail(GSDF_ERR_INVALID, "gsdf_align_best: bad argument");
+    int pick = -1;
+    double score = 0.0;
+    for (int h = 0; h < m; ++h) {
+        const float E = last36[36 * (size_t)h], count = last36[36 * (size_t)h + 28];
+        if (passes[h] <= 0 || (require_converged && !converged[h])) continue;
+        if (!((double)count >= (double)min_count) || !(count > 0.f) || !std::isfinite(E)) continue;   /* no hit: E / count is no score */
+        const double s = (double)E / (double)count;
+        if (pick < 0 || s < score) { pick = h; score = s; }
+    }
+    *best = pick;
+    return GSDF_OK;
+}
+
 /* MapGradPixelSdf::extract_pc's rows (MapGradPixelSdf.cpp:182-195) into `out_dev` (rows_dev != nullptr) or `rows_host` */
 static int surface_cloud_impl(gsdf_ctx* c, float* rows_host, float* rows_dev, int64_t max_n, int64_t* n_out) {
     if (!c || !n_out || max_n < 0) return fail(GSDF_ERR_INVALID, "gsdf_surface_cloud: bad argument");

@@ -198,6 +198,13 @@ int  gsdf_align_grid(long long n);
 void gsdf_launch_align_pass(hipStream_t s, gsdf_table tab, float vs, float inv_vs, const float* pts, long long n,
                             gsdf_align_state* st, double* part /* GSDF_ALIGN_MAXBLK x GSDF_ALIGN_ROW */, float conv_sq, float damping,
                             int max_passes, float* trace /* nullable: max_passes x 36 */);
+/* The same for the n_live runs live[0..n_live) of a batch of m starts, in one pass launch of gsdf_align_grid(n) x n_live
+ * workgroups and one head launch of n_live workgroups (k_align_pass_multi, k_align_head_multi: the bodies of the pair above, so
+ * run h's bytes are those of a single run from st[h]).  st[m]; part[m][gsdf_align_grid(n)][GSDF_ALIGN_ROW]; trace (nullable)
+ * [m][max_passes][36]; last (nullable) [m][36] = the row of run h's latest pass.  A run whose done is set is skipped. */
+void gsdf_launch_align_pass_multi(hipStream_t s, gsdf_table tab, float vs, float inv_vs, const float* pts, long long n,
+                                  gsdf_align_state* st, double* part, const int* live, int n_live, float conv_sq, float damping,
+                                  int max_passes, float* trace, float* last);
 /* The surface cloud (MapGradPixelSdf::extract_pc, MapGradPixelSdf.cpp:182-195): flag = packed key and slot of every voxel that
  * passes the gates, appended through `counter` (keys == nullptr: count only); rows = the 6-float rows from the slots in sorted
  * key order (the caller sorts the pairs with gsdf_sort_pairs_u64) */

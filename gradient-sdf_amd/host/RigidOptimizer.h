@@ -5,6 +5,9 @@
 
 #include "MapGradPixelSdf.h"
 
+#include <cstdint>
+#include <vector>
+
 class RigidOptimizer {
 protected:
     int num_iterations_;
@@ -30,6 +33,8 @@ public:
 
 class RigidPointOptimizer : public RigidOptimizer {
     int last_passes_ = 0;
+    std::vector<int> multi_converged_, multi_passes_;
+    std::vector<float> multi_poses_;
 public:
     RigidPointOptimizer(Sdf* tSDF) : RigidOptimizer(tSDF) {}
     RigidPointOptimizer(int num_iterations, float conv_threshold, float damping, Sdf* tSDF)
@@ -42,6 +47,14 @@ public:
      * (gsdf_align_points): pose_ is the start (source -> map) and receives the result; num_iterations_, conv_threshold_ and
      * damping_ as in optimize().  A MapPixelSdf is refused (std::runtime_error). */
     bool optimize_points(const float* xyz, size_t n);
+    /* optimize_points from each of the m starting poses starts7 (m x 7, e.g. gsdf_align_starts) at once
+     * (gsdf_align_points_multi), then the pick of gsdf_align_best among the converged runs that hit at least min_count points.
+     * Returns the picked index and sets pose_ / last_passes() to that run's, or returns -1 and leaves both alone. */
+    int optimize_points_multi(const float* xyz, size_t n, const float* starts7, int m, int64_t min_count);
+    /* what the last optimize_points_multi call left per start: converged flags, pass counts, poses (m x 7) */
+    const std::vector<int>& multi_converged() const { return multi_converged_; }
+    const std::vector<int>& multi_passes() const { return multi_passes_; }
+    const std::vector<float>& multi_poses() const { return multi_poses_; }
     int last_passes() const { return last_passes_; }
 };
 

@@ -29,3 +29,24 @@ bool RigidPointOptimizer::optimize_points(const float* xyz, size_t n) {
     if (conv) std::cout << "... Convergence after " << passes - 1 << " iterations!" << std::endl;   /* .cpp:89 */
     return conv != 0;
 }
+
+int RigidPointOptimizer::optimize_points_multi(const float* xyz, size_t n, const float* starts7, int m, int64_t min_count) {
+    MapGradPixelSdf* map = dynamic_cast<MapGradPixelSdf*>(tSDF_);
+    if (!map) throw std::runtime_error("RigidPointOptimizer needs a MapGradPixelSdf");
+    if (!starts7 || m < 1) throw std::runtime_error("optimize_points_multi: no starting pose");
+    multi_poses_.assign(starts7, starts7 + (size_t)m * 7);
+    multi_converged_.assign((size_t)m, 0);
+    multi_passes_.assign((size_t)m, 0);
+    std::vector<float> last((size_t)m * 36);
+    int rc = gsdf_align_points_multi(map->ctx_, xyz, (int64_t)n, multi_poses_.data(), m, num_iterations_, conv_threshold_, damping_,
+                                     multi_converged_.data(), multi_passes_.data(), last.data(), nullptr);
+    if (rc != GSDF_OK) throw std::runtime_error(std::string("gsdf_align_points_multi: ") + gsdf_last_error());
+    int best = -1;
+    rc = gsdf_align_best(m, multi_converged_.data(), multi_passes_.data(), last.data(), min_count, 1, &best);
+    if (rc != GSDF_OK) throw std::runtime_error(std::string("gsdf_align_best: ") + gsdf_last_error());
+    if (best < 0) return -1;
+    pose_ = SE3::from_pose7(multi_poses_.data() + (size_t)best * 7);
+    last_passes_ = multi_passes_[(size_t)best];
+    std::cout << "... Start " << best << " of " << m << ": convergence after " << last_passes_ - 1 << " iterations!" << std::endl;
+    return best;
+}

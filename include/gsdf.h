@@ -516,6 +516,58 @@ int gsdf_align_points_dev(gsdf_ctx* c, const float* pts_dev, int64_t n, float po
                           int num_iterations, float conv_threshold, float damping,
                           int* converged, int* passes, float* trace36 /* nullable */);
 
+/* gsdf_align_points from m starting poses at once: one Gauss-Newton run per row of poses7 (m x 7, in / out), all over the same n
+ * points, every pass of every run that has not ended in ONE launch pair (k_align_pass_multi with gsdf_align_grid(n) x live
+ * workgroups, k_align_head_multi with one workgroup per live run).  A single run finds the answer only from inside its basin (about
+ * 2 degrees / 15 cm on the 320x240 test pair); a grid of starts (gsdf_align_starts) and the pick among the runs
+ * (gsdf_align_best) widen it.
+ * For every h the outputs poses7[h], converged[h], passes[h] and the trace rows [0, passes[h]) are equal in BYTES to what
+ * gsdf_align_points returns for (pts, n, poses7[h], the same arguments) on the same map: both run the same device functions
+ * over the same launch geometry per run, the sums in the same order, no floating-point atomics.  The result of run h does not
+ * depend on m, on its position in the batch or on when the other runs end.
+ * trace36 (nullable, m x num_iterations x 36): run h's rows at [h][0 .. passes[h]), zeros from there on.  last36 (nullable,
+ * m x 36): trace row passes[h] - 1, zeros when passes[h] == 0.
+ * n == 0 and num_iterations == 0 behave per run as in the single call.  GSDF_ERR_INVALID with every output untouched: m < 1,
+ * m > GSDF_ALIGN_MAX_STARTS, and what the single call refuses (NULL c / poses7 / converged / passes, NULL pts with n > 0, n < 0,
+ * num_iterations < 0, a base-sdf context).
+ * Synchronous; a waiting pipelined fusion is launched first.  The context's persistent pose, frame log and gsdf_stats are
+ * neither read nor written.  Scratch: m x (256 + gsdf_align_grid(n) x 256) bytes of device memory, kept by the context; a failed
+ * allocation returns GSDF_ERR_HIP with nothing changed.  The host reads the m run states once per batch of launch pairs (the
+ * batches of the single call) and queues the next batch for the runs that have not ended only.  The _dev variant reads the points
+ * in place, as gsdf_align_points_dev. */
+#define GSDF_ALIGN_MAX_STARTS 1024
+int gsdf_align_points_multi(gsdf_ctx* c, const float* pts_host, int64_t n, float* poses7 /* m x 7, in/out */, int m,
+                            int num_iterations, float conv_threshold, float damping,
+                            int* converged /* m */, int* passes /* m */,
+                            float* last36 /* m x 36, nullable */, float* trace36 /* m x num_iterations x 36, nullable */);
+int gsdf_align_points_multi_dev(gsdf_ctx* c, const float* pts_dev, int64_t n, float* poses7 /* m x 7, in/out */, int m,
+                                int num_iterations, float conv_threshold, float damping,
+                                int* converged /* m */, int* passes /* m */,
+                                float* last36 /* m x 36, nullable */, float* trace36 /* m x num_iterations x 36, nullable */);
+
+/* A grid of starting poses around center7 (tx ty tz qx qy qz qw, source -> map).  Host only: no context, no GPU.
+ * Rn = 2 rot_k + 1, Tn = 2 trans_k + 1, *m = Rn^3 Tn^3, always reported (2^31 - 1 if it would pass that).  Start
+ * h = ((((a Rn + b) Rn + c) Tn + d) Tn + e) Tn + f has the rotation vector r = rot_step_rad (a - rot_k, b - rot_k, c - rot_k) and
+ * the offset o = trans_step (d - trans_k, e - trans_k, f - trans_k) in the MAP frame: the source is rotated by r about `pivot`
+ * (source frame; pass the cloud's centroid), then the centre pose is applied, then the offset.  All in double from the float
+ * inputs: qc = the centre's quaternion normalised, Rc its matrix; theta = |r|, qd = (sin(theta / 2) r / theta, cos(theta / 2)) or
+ * the identity when theta == 0, dR its matrix; q_h = qc (x) qd normalised, its sign such that w >= 0;
+ * t_h = Rc (pivot - dR pivot) + tc + o; each of the 7 values rounded to float once.  The middle index (*m - 1) / 2 is the centre
+ * pose itself.  poses7_out == NULL or max_m == 0 is the sizing call; a max_m below *m writes nothing and returns
+ * GSDF_ERR_INVALID.  GSDF_ERR_INVALID also: a NULL centre / pivot / m, negative rot_k / trans_k / max_m, an input that is not
+ * finite, a centre quaternion whose norm is off 1 by more than 1e-4 (*m not written in these cases), *m > GSDF_ALIGN_MAX_STARTS. */
+int gsdf_align_starts(const float center7[7], const float pivot[3], float rot_step_rad, int rot_k, float trans_step, int trans_k,
+                      float* poses7_out, int max_m, int* m);
+
+/* The pick among the m runs of gsdf_align_points_multi.  Host only.  Run h is eligible if passes[h] > 0, converged[h] (unless
+ * !require_converged), count = last36[h][28] >= min_count and > 0, and E = last36[h][0] is finite; its score is (double)E /
+ * (double)count, the mean squared distance of the points that hit.  *best = the eligible run of the smallest score, the lowest
+ * index on a tie, or -1 (still GSDF_OK) if none is eligible.  E is the energy at the pose BEFORE the step of the last executed
+ * pass: for a converged run, whose last step is not applied, that is the returned pose exactly; for one that ran out of passes
+ * it is the pose one step earlier.  GSDF_ERR_INVALID: m < 1 or a NULL argument. */
+int gsdf_align_best(int m, const int* converged, const int* passes, const float* last36, int64_t min_count,
+                    int require_converged, int* best);
+
 /* MapGradPixelSdf::extract_pc (MapGradPixelSdf.cpp:177-195) in memory instead of an ASCII PLY: one row x y z nx ny nz per voxel
  * with weight >= 5 (:184) and |dist * 1.2 g^| < voxel_size / 2 on every axis (:186-188), point = vox2float(idx) - dist * 1.2 g^
  * (:191), normal = -1.2 g^ (:192), all in float; g^ the normalised stored gradient sum.  The reference's row order is its hash

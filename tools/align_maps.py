@@ -7,7 +7,8 @@ B's surface cloud on the device (gsdf_surface_cloud_dev), moves it into a source
 final E / hits, the recovered pose's error, the wall time of the call (median of `--reps` after one warm call), and the HIP-event
 time of one batch of 5 pass + head pairs divided by 5 (conv_threshold = 0, so all five run) next to the event time of
 k_track_pass's launches on map A for a frame of the stream.  One JSON line, also written to profiles/align_points.json (or --out).
---merge goes on to the merge under the recovered pose instead (merge_main): profiles/merge_posed.json."""
+--merge goes on to the merge under the recovered pose instead (merge_main): profiles/merge_posed.json.
+--multi measures the multi-start registration instead (multi_main): profiles/align_multi.json."""
 import argparse, json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -111,17 +112,122 @@ def merge_main(args):
     return 0
 
 
+def multi_main(args):
+    """--multi: the same two maps; B's cloud displaced by 2 degrees about (0.3, -0.5, 0.8) and 0.2 m along (1, 1, -1) / sqrt(3),
+    registered from m = 27 (offsets on the 0.1 m grid, k = 1) and m = 125 (k = 2) starts around the identity with the cloud's
+    centroid as pivot.  Per m: the wall time of ONE gsdf_align_points_multi_dev call next to the wall time of the same starts as m
+    sequential gsdf_align_points_dev calls (both the median of --reps after a warm call, same process), the runs still live at
+    the start of every batch of launch pairs (from the pass counts: a run is queued in a batch iff it has not ended before it),
+    and the HIP-event time of a pass + head pair with all m runs live (a 5-pair batch with conv_threshold = 0, divided by 5).
+    Then the basin: initial errors of 1, 2, 5, 10, 20 degrees crossed with 1, 5, 10, 20, 30 cm, per cell the final error of the
+    single start from the identity and of the picks among the 27 and the 125 starts (converged, at least half the points
+    hitting).  One JSON line, also written to profiles/align_multi.json (or --out)."""
+    import __graft_entry__ as graft
+    import align_points_ref as ref
+    pkg = graft.package()
+    B = pkg.binding
+    W, H, n = 640, 480, args.frames
+    seq = pkg.synth.Sequence("tum", W, H, n_frames=n, seed=0)
+    vs = np.float32(0.01); T = np.float32(10) * vs
+    a = pkg.GradSdf(vs, T, W, H, seq.K, capacity_log2=22)
+    b = pkg.GradSdf(vs, T, W, H, seq.K, capacity_log2=22)
+    frames = [seq.frame(i) for i in range(n)]
+    for i in range(n // 2):
+        a.update(*frames[i])
+    for i in range(n // 2, n):
+        b.update(*frames[i])
+    cloud = b.surface_cloud()[:, :3]
+    npts = len(cloud)
+    u = np.array([1.0, 1.0, -1.0]) / np.sqrt(3.0)
+
+    def errors(pose, Rd, td):
+        Rg = quat_to_R(pose[3:])
+        return (round(float(np.rad2deg(np.arccos(np.clip((np.trace(Rg.T @ Rd) - 1) / 2, -1, 1)))), 4),
+                round(1e3 * float(np.abs(pose[:3].astype(np.float64) - td).max()), 3))
+
+    def grids(src):
+        piv = src.astype(np.float64).mean(axis=0)
+        return {27: B.align_starts(ref.IDENTITY, piv, 0.0, 0, 0.1, 1), 125: B.align_starts(ref.IDENTITY, piv, 0.0, 0, 0.1, 2)}
+
+    def pick(dev, starts, Rd, td):
+        fl, poses, ps, last, _ = a.align_points_multi_dev(dev, npts, starts)
+        best = B.align_best(fl, ps, last, npts // 2, True)
+        if best < 0:
+            return {"pick": -1}
+        ang, terr = errors(poses[best], Rd, td)
+        return {"pick": int(best), "passes": int(ps[best]), "hits": int(last[best, 28]), "rotation_error_deg": ang, "translation_error_mm": terr}
+
+    src, Rd, td = ref.displace(cloud, rot_deg=2.0, tr=tuple(0.2 * u))
+    dev = a.upload(src)
+    timing = {}
+    for m, starts in grids(src).items():
+        fl, poses, ps, last, _ = a.align_points_multi_dev(dev, npts, starts)             # warm, and the pass counts
+        for s in starts[:2]:
+            a.align_points_dev(dev, npts, s)
+        tm, tq = [], []
+        for _ in range(args.reps):
+            t0 = time.perf_counter(); a.align_points_multi_dev(dev, npts, starts); tm.append(time.perf_counter() - t0)
+            t0 = time.perf_counter()
+            for s in starts:
+                a.align_points_dev(dev, npts, s)
+            tq.append(time.perf_counter() - t0)
+        a.timer_start()
+        a.align_points_multi_dev(dev, npts, starts, iters=5, conv=0.0)
+        pair_ms = a.timer_stop_ms() / 5
+        edges, q = [], 0
+        while q < 25:                                   # the batches of the call: first_batch = 5, then next_batch = 8
+            edges.append(q)
+            q += 5 if q == 0 else 8
+        best = B.align_best(fl, ps, last, npts // 2, True)
+        ang, terr = errors(poses[best], Rd, td) if best >= 0 else (None, None)
+        timing[str(m)] = {"multi_call_wall_ms": round(float(np.median(tm)) * 1e3, 3),
+                          "sequential_single_calls_wall_ms": round(float(np.median(tq)) * 1e3, 3),
+                          "ratio_sequential_over_multi": round(float(np.median(tq) / np.median(tm)), 2),
+                          "passes": [int(v) for v in ps], "converged": int(fl.sum()),
+                          "live_at_batch_start": {str(e): int((ps > e).sum()) for e in edges},
+                          "pass_plus_head_pair_event_us_all_live": round(float(pair_ms) * 1e3, 2),
+                          "workgroups_per_pass_all_live": int(min(max((npts + 255) // 256, 1), 512)) * m,
+                          "pick": int(best), "rotation_error_deg": ang, "translation_error_mm": terr}
+    a.timer_start()
+    a.align_points_dev(dev, npts, ref.IDENTITY, iters=5, conv=0.0)
+    single_pair_us = round(a.timer_stop_ms() * 1e3 / 5, 2)
+    basin = []
+    for deg in (1, 2, 5, 10, 20):
+        for cm in (1, 5, 10, 20, 30):
+            src, Rd, td = ref.displace(cloud, rot_deg=float(deg), tr=tuple(0.01 * cm * u))
+            d = a.upload(src)
+            c1, p1, u1, _ = a.align_points_dev(d, npts, ref.IDENTITY)
+            ang1, terr1 = errors(p1, Rd, td)
+            g = grids(src)
+            basin.append({"deg": deg, "cm": cm,
+                          "single": {"converged": bool(c1), "passes": int(u1), "rotation_error_deg": ang1, "translation_error_mm": terr1},
+                          "pick_of_27": pick(d, g[27], Rd, td), "pick_of_125": pick(d, g[125], Rd, td)})
+    out = {"map": "S-tum %dx%d, %d frames (A = first half, B = second half), voxel %.3g m" % (W, H, n, float(vs)),
+           "points": int(npts), "reps": args.reps, "displacement": "2 deg about (0.3, -0.5, 0.8), 0.2 m along (1, 1, -1) / sqrt(3)",
+           "starts": {"27": "offsets {-0.1, 0, 0.1} m per axis", "125": "offsets {-0.2 .. 0.2} m per axis, step 0.1 m"},
+           "timing": timing, "single_pass_plus_head_pair_event_us": single_pair_us, "basin": basin}
+    a.close(); b.close()
+    line = json.dumps(out)
+    print(line)
+    with open(args.out, "w") as f:
+        f.write(line + "\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--merge", action="store_true", help="also merge B into A under the recovered pose (gsdf_merge_from_posed); writes profiles/merge_posed.json")
+    ap.add_argument("--multi", action="store_true", help="multi-start registration (gsdf_align_points_multi) against sequential single calls, and the basin sweep; writes profiles/align_multi.json")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "merge_posed.json" if args.merge else "align_points.json")
+        args.out = os.path.join(ROOT, "profiles", "merge_posed.json" if args.merge else "align_multi.json" if args.multi else "align_points.json")
     if args.merge:
         return merge_main(args)
+    if args.multi:
+        return multi_main(args)
     import __graft_entry__ as graft
     import align_points_ref as ref
     pkg = graft.package()
