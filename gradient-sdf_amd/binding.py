@@ -167,6 +167,18 @@ def load(path=None):
         "gsdf_align_points_multi_dev": (C.c_int, [vp, vp, C.c_int64, fp, C.c_int, C.c_int, C.c_float, C.c_float, i32p, i32p, fp, fp]),
         "gsdf_align_starts": (C.c_int, [fp, fp, C.c_float, C.c_int, C.c_float, C.c_int, fp, C.c_int, C.POINTER(C.c_int)]),
         "gsdf_align_best": (C.c_int, [C.c_int, i32p, i32p, fp, C.c_int64, C.c_int, C.POINTER(C.c_int)]),
+        "gsdf_align_loss_weight": (C.c_int, [C.c_int, C.c_float, C.c_float, fp]),
+        "gsdf_align_points_robust": (C.c_int, [vp, fp, C.c_int64, fp, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float,
+                                               C.POINTER(C.c_int), C.POINTER(C.c_int), fp]),
+        "gsdf_align_points_robust_dev": (C.c_int, [vp, vp, C.c_int64, fp, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float,
+                                                   C.POINTER(C.c_int), C.POINTER(C.c_int), fp]),
+        "gsdf_align_points_multi_robust": (C.c_int, [vp, fp, C.c_int64, fp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float,
+                                                     i32p, i32p, fp, fp]),
+        "gsdf_align_points_multi_robust_dev": (C.c_int, [vp, vp, C.c_int64, fp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float,
+                                                         i32p, i32p, fp, fp]),
+        "gsdf_align_best_robust": (C.c_int, [C.c_int, i32p, i32p, fp, C.c_float, C.c_int, C.POINTER(C.c_int)]),
+        "gsdf_align_residuals": (C.c_int, [vp, fp, C.c_int64, fp, fp, fp]),
+        "gsdf_align_residuals_dev": (C.c_int, [vp, vp, C.c_int64, fp, fp, fp]),
         "gsdf_surface_cloud": (C.c_int, [vp, fp, C.c_int64, i64p]),
         "gsdf_surface_cloud_dev": (C.c_int, [vp, vp, C.c_int64, i64p]),
         "gsdf_block_keys_dev": (C.c_int, [vp, vp, C.c_int64, C.POINTER(C.c_int64)]),
@@ -233,6 +245,8 @@ ABI_SYMBOLS = [
     "gsdf_rccl_comm_destroy",
     "gsdf_query", "gsdf_get_voxels", "gsdf_align_points", "gsdf_align_points_dev", "gsdf_surface_cloud", "gsdf_surface_cloud_dev",
     "gsdf_align_points_multi", "gsdf_align_points_multi_dev", "gsdf_align_starts", "gsdf_align_best",
+    "gsdf_align_loss_weight", "gsdf_align_points_robust", "gsdf_align_points_robust_dev", "gsdf_align_points_multi_robust",
+    "gsdf_align_points_multi_robust_dev", "gsdf_align_best_robust", "gsdf_align_residuals", "gsdf_align_residuals_dev",
     "gsdf_raycast", "gsdf_raycast_dev", "gsdf_raycast_counters", "gsdf_extract_mesh",
     "gsdf_extract_mesh_indexed", "gsdf_mesh_components", "gsdf_extract_mesh_indexed_filtered", "gsdf_gradient_angles", "gsdf_gradient_stats",
     "gsdf_dev_alloc", "gsdf_dev_free", "gsdf_dev_upload", "gsdf_dev_download", "gsdf_timer_start", "gsdf_timer_stop_ms",
@@ -313,6 +327,42 @@ def align_best(converged, passes, last, min_count=1, require_converged=True, lib
     i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))                 # noqa: E731
     best = C.c_int(-2)
     rc = L.gsdf_align_best(len(fl), i32(fl), i32(ps), _fp(la), int(min_count), int(bool(require_converged)), C.byref(best))
+    if rc != GSDF_OK:
+        raise GsdfError(rc, L.gsdf_last_error().decode())
+    return best.value
+
+
+LOSS_L2, LOSS_CAUCHY, LOSS_HUBER, LOSS_TUKEY, LOSS_TRUNC_L2 = 0, 1, 2, 3, 4      # ps_optimizer/loss.h:41-48, as gsdf_ba_set_loss
+
+
+def align_loss_weight(loss, scale, phi, lib=None):
+    """gsdf_align_loss_weight (host only) over an array: the float32 weights the robust pass gives the distances `phi`"""
+    L = load() if lib is None else lib
+    x = _f32(phi)
+    out = np.empty(x.shape, np.float32)
+    w = C.c_float(0)
+    fn, lo, sc, ref = L.gsdf_align_loss_weight, int(loss), np.float32(scale), C.byref(w)
+    flat_in, flat_out = x.reshape(-1), out.reshape(-1)
+    for i in range(flat_in.size):
+        rc = fn(lo, sc, flat_in[i], ref)
+        if rc != GSDF_OK:
+            raise GsdfError(rc, L.gsdf_last_error().decode())
+        flat_out[i] = w.value
+    return out
+
+
+def align_best_robust(converged, passes, last, min_wsum=1.0, require_converged=True, lib=None):
+    """gsdf_align_best_robust (host only): the index of the run with the smallest E / wsum among those that executed a pass,
+    converged (if required) and gathered a weight sum of at least min_wsum, or -1"""
+    L = load() if lib is None else lib
+    fl = np.ascontiguousarray(converged, dtype=np.int32).reshape(-1)
+    ps = np.ascontiguousarray(passes, dtype=np.int32).reshape(-1)
+    la = _f32(last).reshape(-1, 38)
+    if not (len(fl) == len(ps) == len(la)):
+        raise ValueError("align_best_robust: converged, passes and last differ in length")
+    i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))                 # noqa: E731
+    best = C.c_int(-2)
+    rc = L.gsdf_align_best_robust(len(fl), i32(fl), i32(ps), _fp(la), np.float32(min_wsum), int(bool(require_converged)), C.byref(best))
     if rc != GSDF_OK:
         raise GsdfError(rc, L.gsdf_last_error().decode())
     return best.value
@@ -810,6 +860,69 @@ class GradSdf:
         """the same over n x 3 floats already in device memory, as align_points_dev"""
         p = pts_dev if isinstance(pts_dev, C.c_void_p) or pts_dev is None else C.c_void_p(int(pts_dev))
         return self._align_multi(self.L.gsdf_align_points_multi_dev, p, n, poses7, iters, conv, damping)
+
+    # -- the same with a robust loss; residuals under a pose ------------------------------------------
+    def _align_robust(self, fn, pts_arg, n, pose7, loss, scale, iters, conv, damping):
+        p = _f32(pose7).reshape(7).copy()
+        flag, passes = C.c_int(0), C.c_int(0)
+        trace = np.zeros((max(int(iters), 1), 38), np.float32)
+        self._chk(fn(self.h, pts_arg, int(n), _fp(p), int(iters), np.float32(conv), np.float32(damping), int(loss), np.float32(scale),
+                     C.byref(flag), C.byref(passes), _fp(trace)))
+        return bool(flag.value), p, passes.value, trace[:passes.value]
+
+    def align_points_robust(self, pts, pose7, loss, scale, iters=25, conv=1e-3, damping=1.0):
+        """gsdf_align_points_robust: align_points with every term of a point multiplied by the weight the loss (LOSS_L2 ..
+        LOSS_TRUNC_L2) gives its distance at `scale` metres.  Returns (converged, pose7, passes, trace [passes, 38]); the rows as
+        align_points', then [36] the weight sum and [37] the number of points of weight > 0."""
+        x = _f32(pts).reshape(-1, 3)
+        return self._align_robust(self.L.gsdf_align_points_robust, _fp(x) if len(x) else None, len(x), pose7, loss, scale, iters, conv,
+                                  damping)
+
+    def align_points_robust_dev(self, pts_dev, n, pose7, loss, scale, iters=25, conv=1e-3, damping=1.0):
+        """the same over n x 3 floats already in device memory, as align_points_dev"""
+        p = pts_dev if isinstance(pts_dev, C.c_void_p) or pts_dev is None else C.c_void_p(int(pts_dev))
+        return self._align_robust(self.L.gsdf_align_points_robust_dev, p, n, pose7, loss, scale, iters, conv, damping)
+
+    def _align_multi_robust(self, fn, pts_arg, n, poses7, loss, scale, iters, conv, damping):
+        p = _f32(poses7).reshape(-1, 7).copy()
+        m, iters = len(p), int(iters)
+        flags, passes = np.zeros(m, np.int32), np.zeros(m, np.int32)
+        last = np.zeros((m, 38), np.float32)
+        trace = np.zeros((m, max(iters, 1), 38), np.float32)
+        i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))             # noqa: E731
+        self._chk(fn(self.h, pts_arg, int(n), _fp(p), m, iters, np.float32(conv), np.float32(damping), int(loss), np.float32(scale),
+                     i32(flags), i32(passes), _fp(last), _fp(trace)))
+        return flags.astype(bool), p, passes, last, trace[:, :max(iters, 0)]
+
+    def align_points_multi_robust(self, pts, poses7, loss, scale, iters=25, conv=1e-3, damping=1.0):
+        """gsdf_align_points_multi_robust: align_points_robust from every row of `poses7` [m, 7] at once, each run equal in bytes
+        to the single call.  Returns (converged [m], poses [m, 7], passes [m], last [m, 38], trace [m, iters, 38]).  Pick:
+        align_best_robust."""
+        x = _f32(pts).reshape(-1, 3)
+        return self._align_multi_robust(self.L.gsdf_align_points_multi_robust, _fp(x) if len(x) else None, len(x), poses7, loss, scale,
+                                        iters, conv, damping)
+
+    def align_points_multi_robust_dev(self, pts_dev, n, poses7, loss, scale, iters=25, conv=1e-3, damping=1.0):
+        """the same over n x 3 floats already in device memory, as align_points_dev"""
+        p = pts_dev if isinstance(pts_dev, C.c_void_p) or pts_dev is None else C.c_void_p(int(pts_dev))
+        return self._align_multi_robust(self.L.gsdf_align_points_multi_robust_dev, p, n, poses7, loss, scale, iters, conv, damping)
+
+    def _residuals(self, fn, pts_arg, n, pose7):
+        p = _f32(pose7).reshape(7)
+        phi, w = np.zeros(int(n), np.float32), np.zeros(int(n), np.float32)
+        self._chk(fn(self.h, pts_arg, int(n), _fp(p), _fp(phi) if n else None, _fp(w) if n else None))
+        return phi, w
+
+    def align_residuals(self, pts, pose7):
+        """gsdf_align_residuals: (phi [n], w [n]) = the distance and the voxel weight each point of `pts` [n, 3] meets under
+        `pose7`, as the registration's pass sees them; both 0 where the voxel is missing or the point is not finite"""
+        x = _f32(pts).reshape(-1, 3)
+        return self._residuals(self.L.gsdf_align_residuals, _fp(x) if len(x) else None, len(x), pose7)
+
+    def align_residuals_dev(self, pts_dev, n, pose7):
+        """the same over n x 3 floats already in device memory; the results come back as host arrays"""
+        p = pts_dev if isinstance(pts_dev, C.c_void_p) or pts_dev is None else C.c_void_p(int(pts_dev))
+        return self._residuals(self.L.gsdf_align_residuals_dev, p, n, pose7)
 
     def surface_cloud(self):
         """gsdf_surface_cloud:MapGradPixelSdf::extract_pc's rows [n, 6] = x y z nx ny nz, in (z, y, x) key order"""

@@ -3,6 +3,8 @@
  *
  *   k_align_pass / k_align_head   RigidPointOptimizer::optimize_sampled, :70-95, over n given points   RigidPointOptimizer.cpp:51-96
  *   k_align_pass_multi / k_align_head_multi   the same two bodies for a batch of starting poses, one run each, side by side
+ *   k_align_pass_robust / k_align_head_robust (and _multi_robust)   the same bodies with a robust loss's weight on every term
+ *   k_align_residuals   the distance and the voxel weight each point meets under a pose: what a pass sees, per point
  *   k_surface_flag / k_surface_rows   MapGradPixelSdf::extract_pc's rows, in memory                    MapGradPixelSdf.cpp:177-195
  *
  * The reference's tracker turns the depth image into points (:62-69) and never looks at the image again (:70-82); the pass
@@ -25,12 +27,17 @@
  * Wave = 64 lanes.
  */
 #include "gsdf_kernels.h"
+#include "gsdf_align_loss.h"
 #include "gsdf_math.h"
 #include "gsdf_sample.h"
 
 #include <hip/hip_runtime.h>
 
 #define ALIGN_WAVES (GSDF_ALIGN_BLOCK / 64)
+/* the sums of a pass: the 29 of GSDF_TRACK_NSUM, and for a robust pass the weight sum (slot 29) and the inlier count (slot 30) */
+#define ALIGN_NSUM(ROBUST) ((ROBUST) ? GSDF_ALIGN_NSUM_ROBUST : GSDF_TRACK_NSUM)
+/* floats of a trace row: 36, and for a robust pass 38 ([36] = the weight sum, [37] = the inlier count) */
+#define ALIGN_TRACE(ROBUST) ((ROBUST) ? 38 : 36)
 
 int gsdf_align_grid(long long n) {
     const long long b = (n + GSDF_ALIGN_BLOCK - 1) / GSDF_ALIGN_BLOCK;
@@ -38,16 +45,22 @@ int gsdf_align_grid(long long n) {
 }
 
 /* One pass over the points for one run: part[workgroup][32] = this workgroup's 29 sums (slots 29..31 zero).  The body of
- * k_align_pass and of k_align_pass_multi: blockIdx.x / gridDim.x are the workgroup's index and count within the run. */
+ * k_align_pass and of k_align_pass_multi: blockIdx.x / gridDim.x are the workgroup's index and count within the run.
+ * ROBUST (k_align_pass_robust, k_align_pass_multi_robust): every term carries the weight rw = gsdf_align_weight(loss, scale, phi)
+ * of its point -- wphi = rw phi and wJ = rw J, then wphi phi, wphi J[a], wJ[a] J[b], one float operation each -- and the row
+ * has 31 sums: slot 29 the sum of the weights, slot 30 the number of points with rw > 0.  With loss = L2, rw = 1 and every
+ * product with it is exact: slots 0..28 are the plain pass's bit for bit. */
+template <bool ROBUST>
 __device__ __forceinline__ void align_pass_body(gsdf_table tab, float vs, float inv_vs, const float* __restrict__ pts, long long n,
                                                 const gsdf_align_state* __restrict__ st, double* __restrict__ part,
-                                                double (&rows)[ALIGN_WAVES][GSDF_ALIGN_ROW]) {
+                                                double (&rows)[ALIGN_WAVES][GSDF_ALIGN_ROW], int loss = 0, float scale = 0.f) {
+    constexpr int NSUM = ALIGN_NSUM(ROBUST);
     float R[9];
     gsdf_quat_to_R(st->pose7 + 3, R);                                      /* :53 */
     const gsdf_v3 t = { st->pose7[0], st->pose7[1], st->pose7[2] };        /* :54 */
-    double acc[GSDF_TRACK_NSUM];
+    double acc[NSUM];
 #pragma unroll
-    for (int v = 0; v < GSDF_TRACK_NSUM; ++v) acc[v] = 0.0;
+    for (int v = 0; v < NSUM; ++v) acc[v] = 0.0;
     const long long stride = (long long)gridDim.x * GSDF_ALIGN_BLOCK;
     for (long long i = (long long)blockIdx.x * GSDF_ALIGN_BLOCK + threadIdx.x; i < n; i += stride) {
         const gsdf_v3 x = { pts[3 * i], pts[3 * i + 1], pts[3 * i + 2] };
@@ -61,32 +74,51 @@ __device__ __forceinline__ void align_pass_body(gsdf_table tab, float vs, float 
         if (w0 > 0.f) {
             const gsdf_v3 pxg = gsdf_cross3(p, g);
             const float J[6] = { g.x, g.y, g.z, pxg.x, pxg.y, pxg.z };     /* :77-78 */
-            acc[0] += (double)(phi * phi);                                 /* :76 */
+            if constexpr (ROBUST) {
+                const float rw = gsdf_align_weight(loss, scale, phi);
+                const float wphi = rw * phi;
+                float wJ[6];
 #pragma unroll
-            for (int a = 0; a < 6; ++a) acc[1 + a] += (double)(phi * J[a]);   /* :79 */
-            int q = 7;
+                for (int a = 0; a < 6; ++a) wJ[a] = rw * J[a];
+                acc[0] += (double)(wphi * phi);
 #pragma unroll
-            for (int a = 0; a < 6; ++a)
+                for (int a = 0; a < 6; ++a) acc[1 + a] += (double)(wphi * J[a]);
+                int q = 7;
 #pragma unroll
-                for (int b = a; b < 6; ++b) acc[q++] += (double)(J[a] * J[b]);   /* :80 */
-            acc[28] += 1.0;                                                /* :81 */
+                for (int a = 0; a < 6; ++a)
+#pragma unroll
+                    for (int b = a; b < 6; ++b) acc[q++] += (double)(wJ[a] * J[b]);
+                acc[28] += 1.0;
+                acc[29] += (double)rw;
+                if (rw > 0.f) acc[30] += 1.0;
+            } else {
+                acc[0] += (double)(phi * phi);                             /* :76 */
+#pragma unroll
+                for (int a = 0; a < 6; ++a) acc[1 + a] += (double)(phi * J[a]);   /* :79 */
+                int q = 7;
+#pragma unroll
+                for (int a = 0; a < 6; ++a)
+#pragma unroll
+                    for (int b = a; b < 6; ++b) acc[q++] += (double)(J[a] * J[b]);   /* :80 */
+                acc[28] += 1.0;                                            /* :81 */
+            }
         }
     }
     /* the butterfly: afterwards every lane holds the wave's sums (a + b is commutative, so all lanes hold the same bits) */
 #pragma unroll
-    for (int v = 0; v < GSDF_TRACK_NSUM; ++v) {
+    for (int v = 0; v < NSUM; ++v) {
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) acc[v] += __shfl_xor(acc[v], m, 64);
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) {
 #pragma unroll
-        for (int v = 0; v < GSDF_TRACK_NSUM; ++v) rows[wave][v] = acc[v];
+        for (int v = 0; v < NSUM; ++v) rows[wave][v] = acc[v];
     }
     __syncthreads();
     if (threadIdx.x < GSDF_ALIGN_ROW) {
         double s = 0.0;
-        if (threadIdx.x < GSDF_TRACK_NSUM) {
+        if (threadIdx.x < NSUM) {
             s = rows[0][threadIdx.x];
 #pragma unroll
             for (int wv = 1; wv < ALIGN_WAVES; ++wv) s += rows[wv][threadIdx.x];
@@ -100,7 +132,7 @@ __global__ __launch_bounds__(GSDF_ALIGN_BLOCK) void k_align_pass(gsdf_table tab,
                                                                  double* __restrict__ part) {
     if (st->done) return;                                                  /* queued beyond the end of the run */
     __shared__ double rows[ALIGN_WAVES][GSDF_ALIGN_ROW];
-    align_pass_body(tab, vs, inv_vs, pts, n, st, part, rows);
+    align_pass_body<false>(tab, vs, inv_vs, pts, n, st, part, rows);
 }
 
 /* The same pass for the live runs of a batch of starts: workgroup (x, y) is workgroup x of run live[y].  st[m], part[m][gridDim.x][32]. */
@@ -110,7 +142,26 @@ __global__ __launch_bounds__(GSDF_ALIGN_BLOCK) void k_align_pass_multi(gsdf_tabl
     const int h = live[blockIdx.y];
     if (st[h].done) return;                                                /* ended inside this batch */
     __shared__ double rows[ALIGN_WAVES][GSDF_ALIGN_ROW];
-    align_pass_body(tab, vs, inv_vs, pts, n, st + h, part + (size_t)h * gridDim.x * GSDF_ALIGN_ROW, rows);
+    align_pass_body<false>(tab, vs, inv_vs, pts, n, st + h, part + (size_t)h * gridDim.x * GSDF_ALIGN_ROW, rows);
+}
+
+/* the two passes with the loss's weights: the same body, 31 sums per row */
+__global__ __launch_bounds__(GSDF_ALIGN_BLOCK) void k_align_pass_robust(gsdf_table tab, float vs, float inv_vs, const float* __restrict__ pts,
+                                                                        long long n, const gsdf_align_state* __restrict__ st,
+                                                                        double* __restrict__ part, int loss, float scale) {
+    if (st->done) return;
+    __shared__ double rows[ALIGN_WAVES][GSDF_ALIGN_ROW];
+    align_pass_body<true>(tab, vs, inv_vs, pts, n, st, part, rows, loss, scale);
+}
+__global__ __launch_bounds__(GSDF_ALIGN_BLOCK) void k_align_pass_multi_robust(gsdf_table tab, float vs, float inv_vs,
+                                                                              const float* __restrict__ pts, long long n,
+                                                                              const gsdf_align_state* __restrict__ st,
+                                                                              double* __restrict__ part, const int* __restrict__ live,
+                                                                              int loss, float scale) {
+    const int h = live[blockIdx.y];
+    if (st[h].done) return;
+    __shared__ double rows[ALIGN_WAVES][GSDF_ALIGN_ROW];
+    align_pass_body<true>(tab, vs, inv_vs, pts, n, st + h, part + (size_t)h * gridDim.x * GSDF_ALIGN_ROW, rows, loss, scale);
 }
 
 /* The head of one pass (:86-95): totals, solve, stop test, pose update, trace row.  The partial rows are staged through LDS
@@ -119,20 +170,23 @@ __global__ __launch_bounds__(GSDF_ALIGN_BLOCK) void k_align_pass_multi(gsdf_tabl
  * the staged rows in index order. */
 #define ALIGN_HEAD_THREADS 256
 #define ALIGN_HEAD_ROWS 64
-/* the body of k_align_head and of k_align_head_multi; `last` (nullable, 36 floats) receives every executed pass's row in turn */
+/* the body of k_align_head and of k_align_head_multi; `last` (nullable, 36 floats) receives every executed pass's row in turn.
+ * ROBUST: 31 totals, and rows of 38 floats whose [36] and [37] are the weight sum and the inlier count; the rest is the same. */
+template <bool ROBUST>
 __device__ __forceinline__ void align_head_body(gsdf_align_state* __restrict__ st, const double* __restrict__ part, int grid, float conv_sq,
                                                 float damping, int max_passes, float* __restrict__ trace, float* __restrict__ last,
                                                 double (&stage)[ALIGN_HEAD_ROWS * GSDF_ALIGN_ROW], float (&tot)[GSDF_ALIGN_ROW]) {
+    constexpr int NSUM = ALIGN_NSUM(ROBUST), TRACE = ALIGN_TRACE(ROBUST);
     double s = 0.0;
     for (int b0 = 0; b0 < grid; b0 += ALIGN_HEAD_ROWS) {
         const int nrow = min(ALIGN_HEAD_ROWS, grid - b0);
         for (int e = threadIdx.x; e < nrow * GSDF_ALIGN_ROW; e += ALIGN_HEAD_THREADS) stage[e] = part[(size_t)b0 * GSDF_ALIGN_ROW + e];
         __syncthreads();
-        if (threadIdx.x < GSDF_TRACK_NSUM)
+        if (threadIdx.x < NSUM)
             for (int r = 0; r < nrow; ++r) s += stage[r * GSDF_ALIGN_ROW + threadIdx.x];
         __syncthreads();
     }
-    if (threadIdx.x < GSDF_TRACK_NSUM) tot[threadIdx.x] = (float)s;        /* the one rounding of each sum */
+    if (threadIdx.x < NSUM) tot[threadIdx.x] = (float)s;        /* the one rounding of each sum */
     __syncthreads();
     if (threadIdx.x != 0) return;
     float gvec[6], Hm[36];
@@ -153,12 +207,13 @@ __device__ __forceinline__ void align_head_body(gsdf_align_state* __restrict__ s
                       gsdf_sum3(xi[3] * xi[3], xi[4] * xi[4], xi[5] * xi[5]);
     const int k = st->passes;
     if (trace) {
-        float* tr = trace + (size_t)36 * k;
+        float* tr = trace + (size_t)TRACE * k;
 #pragma unroll
         for (int i = 0; i < GSDF_TRACK_NSUM; ++i) tr[i] = tot[i];
 #pragma unroll
         for (int i = 0; i < 6; ++i) tr[29 + i] = xi[i];
         tr[35] = nrm;
+        if constexpr (ROBUST) { tr[36] = tot[29]; tr[37] = tot[30]; }
     }
     if (last) {
 #pragma unroll
@@ -166,6 +221,7 @@ __device__ __forceinline__ void align_head_body(gsdf_align_state* __restrict__ s
 #pragma unroll
         for (int i = 0; i < 6; ++i) last[29 + i] = xi[i];
         last[35] = nrm;
+        if constexpr (ROBUST) { last[36] = tot[29]; last[37] = tot[30]; }
     }
     st->passes = k + 1;
     if (nrm < conv_sq) {                                                   /* :88-91: xi is NOT applied */
@@ -195,7 +251,7 @@ __global__ __launch_bounds__(ALIGN_HEAD_THREADS) void k_align_head(gsdf_align_st
     if (st->done) return;
     __shared__ double stage[ALIGN_HEAD_ROWS * GSDF_ALIGN_ROW];
     __shared__ float tot[GSDF_ALIGN_ROW];
-    align_head_body(st, part, grid, conv_sq, damping, max_passes, trace, nullptr, stage, tot);
+    align_head_body<false>(st, part, grid, conv_sq, damping, max_passes, trace, nullptr, stage, tot);
 }
 
 /* The heads of the live runs side by side: workgroup y is the head of run live[y] on its rows part[h][grid][32], its state, its
@@ -208,25 +264,96 @@ __global__ __launch_bounds__(ALIGN_HEAD_THREADS) void k_align_head_multi(gsdf_al
     if (st[h].done) return;
     __shared__ double stage[ALIGN_HEAD_ROWS * GSDF_ALIGN_ROW];
     __shared__ float tot[GSDF_ALIGN_ROW];
-    align_head_body(st + h, part + (size_t)h * grid * GSDF_ALIGN_ROW, grid, conv_sq, damping, max_passes,
-                    trace ? trace + (size_t)h * max_passes * 36 : nullptr, last ? last + (size_t)h * 36 : nullptr, stage, tot);
+    align_head_body<false>(st + h, part + (size_t)h * grid * GSDF_ALIGN_ROW, grid, conv_sq, damping, max_passes,
+                           trace ? trace + (size_t)h * max_passes * 36 : nullptr, last ? last + (size_t)h * 36 : nullptr, stage, tot);
+}
+
+/* the two heads over 31 totals, with rows of 38 floats */
+__global__ __launch_bounds__(ALIGN_HEAD_THREADS) void k_align_head_robust(gsdf_align_state* __restrict__ st, const double* __restrict__ part,
+                                                                          int grid, float conv_sq, float damping, int max_passes,
+                                                                          float* __restrict__ trace) {
+    if (st->done) return;
+    __shared__ double stage[ALIGN_HEAD_ROWS * GSDF_ALIGN_ROW];
+    __shared__ float tot[GSDF_ALIGN_ROW];
+    align_head_body<true>(st, part, grid, conv_sq, damping, max_passes, trace, nullptr, stage, tot);
+}
+__global__ __launch_bounds__(ALIGN_HEAD_THREADS) void k_align_head_multi_robust(gsdf_align_state* __restrict__ st,
+                                                                                const double* __restrict__ part, int grid, float conv_sq,
+                                                                                float damping, int max_passes, float* __restrict__ trace,
+                                                                                float* __restrict__ last, const int* __restrict__ live) {
+    const int h = live[blockIdx.x];
+    if (st[h].done) return;
+    __shared__ double stage[ALIGN_HEAD_ROWS * GSDF_ALIGN_ROW];
+    __shared__ float tot[GSDF_ALIGN_ROW];
+    align_head_body<true>(st + h, part + (size_t)h * grid * GSDF_ALIGN_ROW, grid, conv_sq, damping, max_passes,
+                          trace ? trace + (size_t)h * max_passes * 38 : nullptr, last ? last + (size_t)h * 38 : nullptr, stage, tot);
 }
 
 void gsdf_launch_align_pass(hipStream_t s, gsdf_table tab, float vs, float inv_vs, const float* pts, long long n,
-                            gsdf_align_state* st, double* part, float conv_sq, float damping, int max_passes, float* trace) {
+                            gsdf_align_state* st, double* part, float conv_sq, float damping, int max_passes, float* trace,
+                            int loss, float scale) {
     const int grid = gsdf_align_grid(n);
+    if (loss >= 0) {
+        hipLaunchKernelGGL(k_align_pass_robust, dim3(grid), dim3(GSDF_ALIGN_BLOCK), 0, s, tab, vs, inv_vs, pts, n, st, part, loss, scale);
+        hipLaunchKernelGGL(k_align_head_robust, dim3(1), dim3(ALIGN_HEAD_THREADS), 0, s, st, part, grid, conv_sq, damping, max_passes, trace);
+        return;
+    }
     hipLaunchKernelGGL(k_align_pass, dim3(grid), dim3(GSDF_ALIGN_BLOCK), 0, s, tab, vs, inv_vs, pts, n, st, part);
     hipLaunchKernelGGL(k_align_head, dim3(1), dim3(ALIGN_HEAD_THREADS), 0, s, st, part, grid, conv_sq, damping, max_passes, trace);
 }
 
 void gsdf_launch_align_pass_multi(hipStream_t s, gsdf_table tab, float vs, float inv_vs, const float* pts, long long n,
                                   gsdf_align_state* st, double* part, const int* live, int n_live, float conv_sq, float damping,
-                                  int max_passes, float* trace, float* last) {
+                                  int max_passes, float* trace, float* last, int loss, float scale) {
     if (n_live < 1) return;
     const int grid = gsdf_align_grid(n);
+    if (loss >= 0) {
+        hipLaunchKernelGGL(k_align_pass_multi_robust, dim3(grid, n_live), dim3(GSDF_ALIGN_BLOCK), 0, s, tab, vs, inv_vs, pts, n, st, part,
+                           live, loss, scale);
+        hipLaunchKernelGGL(k_align_head_multi_robust, dim3(n_live), dim3(ALIGN_HEAD_THREADS), 0, s, st, part, grid, conv_sq, damping,
+                           max_passes, trace, last, live);
+        return;
+    }
     hipLaunchKernelGGL(k_align_pass_multi, dim3(grid, n_live), dim3(GSDF_ALIGN_BLOCK), 0, s, tab, vs, inv_vs, pts, n, st, part, live);
     hipLaunchKernelGGL(k_align_head_multi, dim3(n_live), dim3(ALIGN_HEAD_THREADS), 0, s, st, part, grid, conv_sq, damping, max_passes,
                        trace, last, live);
+}
+
+/* ------------------------------------------------------------------------------------------------
+ * residuals under a pose
+ * ---------------------------------------------------------------------------------------------- */
+struct align_pose7 { float v[7]; };
+/* What a pass from `pose` sees per point: p = R x + t as align_pass_body forms it, then gsdf_grad_sample.  w[i] = the voxel's
+ * weight, 0 for a missing voxel or a point that is not finite after the transform; phi[i] = the distance, 0 where w[i] == 0.
+ * One lane per point (grid-stride behind the grid cap), no reductions. */
+__global__ __launch_bounds__(256) void k_align_residuals(gsdf_table tab, float vs, float inv_vs, const float* __restrict__ pts, long long n,
+                                                         align_pose7 pose, float* __restrict__ phi_out, float* __restrict__ w_out) {
+    float R[9];
+    gsdf_quat_to_R(pose.v + 3, R);
+    const gsdf_v3 t = { pose.v[0], pose.v[1], pose.v[2] };
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        const gsdf_v3 x = { pts[3 * i], pts[3 * i + 1], pts[3 * i + 2] };
+        const gsdf_v3 Rx = gsdf_matvec(R, x);
+        const gsdf_v3 p = { Rx.x + t.x, Rx.y + t.y, Rx.z + t.z };
+        float w0 = 0.f, phi = 0.f;
+        if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
+            gsdf_v3 g;
+            gsdf_grad_sample(tab, vs, inv_vs, p, w0, phi, g);
+        }
+        phi_out[i] = phi;
+        w_out[i] = w0;
+    }
+}
+
+void gsdf_launch_align_residuals(hipStream_t s, gsdf_table tab, float vs, float inv_vs, const float* pts, long long n,
+                                 const float pose7[7], float* phi_out, float* w_out) {
+    if (n <= 0) return;
+    align_pose7 pose;
+    for (int i = 0; i < 7; ++i) pose.v[i] = pose7[i];
+    const long long b = (n + 255) / 256;
+    hipLaunchKernelGGL(k_align_residuals, dim3((unsigned int)(b > 65536 ? 65536 : b)), dim3(256), 0, s, tab, vs, inv_vs, pts, n, pose,
+                       phi_out, w_out);
 }
 
 /* ------------------------------------------------------------------------------------------------

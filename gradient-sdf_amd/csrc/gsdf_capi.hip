@@ -10,6 +10,7 @@
 #include "../../include/gsdf_mc_tables.h"
 #include "gsdf_ctx.h"
 #include "gsdf_kernels.h"
+#include "gsdf_align_loss.h"
 #include "gsdf_math.h"
 #include "gsdf_sweep.h"
 
@@ -1592,14 +1593,16 @@ int gsdf_get_voxels(gsdf_ctx* c, const int32_t* keys_host, int64_t n, float* pay
 
 /* RigidPointOptimizer.cpp:51-96 over points already on the device.  Pairs of pass + head are queued in batches (both kernels
  * return at once when the run has ended); the host reads the run's small state once per batch, never per pass. */
+/* loss < 0: the plain pair and rows of 36 floats (gsdf_align_points); loss in 0..4: the robust pair and rows of 38 */
 static int align_points_impl(gsdf_ctx* c, const float* pts_dev, int64_t n, float pose7[7], int num_iterations, float conv_threshold,
-                             float damping, int* converged, int* passes, float* trace36) {
+                             float damping, int* converged, int* passes, float* trace36, int loss = -1, float scale = 0.f) {
+    const size_t row = loss >= 0 ? 38 : 36;
     const size_t part_bytes = (size_t)GSDF_ALIGN_MAXBLK * GSDF_ALIGN_ROW * sizeof(double);
     HIP_TRY(c->align.grow(256 + part_bytes));
     gsdf_align_state* d_st = c->align.as<gsdf_align_state>();
     double* d_part = (double*)(c->align.as<char>() + 256);
     gsdf_dev<float> d_trace;
-    if (trace36) HIP_TRY(d_trace.alloc((size_t)num_iterations * 36));
+    if (trace36) HIP_TRY(d_trace.alloc((size_t)num_iterations * row));
     gsdf_align_state h;
     std::memcpy(h.pose7, pose7, sizeof(h.pose7));
     h.done = 0; h.converged = 0; h.passes = 0;
@@ -1610,7 +1613,7 @@ static int align_points_impl(gsdf_ctx* c, const float* pts_dev, int64_t n, float
         const int batch = std::min(num_iterations - queued, queued == 0 ? c->first_batch : c->next_batch);
         for (int k = 0; k < batch; ++k)
             gsdf_launch_align_pass(c->stream, c->tab, c->voxel_size, c->voxel_size_inv, pts_dev, n, d_st, d_part, conv_sq, damping,
-                                   num_iterations, d_trace);
+                                   num_iterations, d_trace, loss, scale);
         HIP_TRY(hipGetLastError());
         queued += batch;
         HIP_TRY(hipMemcpyAsync(&h, d_st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
@@ -1618,7 +1621,7 @@ static int align_points_impl(gsdf_ctx* c, const float* pts_dev, int64_t n, float
         if (h.done) break;
     }
     if (trace36 && h.passes > 0) {
-        HIP_TRY(hipMemcpyAsync(trace36, d_trace, (size_t)h.passes * 36 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(trace36, d_trace, (size_t)h.passes * row * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     std::memcpy(pose7, h.pose7, sizeof(h.pose7));
@@ -1665,7 +1668,8 @@ int gsdf_align_points(gsdf_ctx* c, const float* pts_host, int64_t n, float pose7
  * 64 m), then from byte 256 m the partial rows part[m][grid][GSDF_ALIGN_ROW].  The batches are those of the single call; after
  * each the host reads the m states and packs the runs that have not ended into the list of the next batch's launches. */
 static int align_multi_impl(gsdf_ctx* c, const float* pts_dev, int64_t n, float* poses7, int m, int num_iterations, float conv_threshold,
-                            float damping, int* converged, int* passes, float* last36, float* trace36) {
+                            float damping, int* converged, int* passes, float* last36, float* trace36, int loss = -1, float scale = 0.f) {
+    const size_t row = loss >= 0 ? 38 : 36;                                /* as align_points_impl */
     const int grid = gsdf_align_grid(n);
     const size_t need = (size_t)m * (256 + (size_t)grid * GSDF_ALIGN_ROW * sizeof(double));
     if (c->align.bytes() < need) {                                         /* a failed allocation leaves the old scratch in place */
@@ -1677,9 +1681,9 @@ static int align_multi_impl(gsdf_ctx* c, const float* pts_dev, int64_t n, float*
     int* d_live = (int*)(c->align.as<char>() + (size_t)m * 64);
     double* d_part = (double*)(c->align.as<char>() + (size_t)m * 256);
     gsdf_dev<float> d_trace, d_last;
-    const size_t trace_n = (size_t)m * num_iterations * 36;
+    const size_t trace_n = (size_t)m * num_iterations * row;
     if (trace36) HIP_TRY(d_trace.alloc(trace_n));
-    if (last36) HIP_TRY(d_last.alloc((size_t)m * 36));
+    if (last36) HIP_TRY(d_last.alloc((size_t)m * row));
     std::vector<gsdf_align_state> h((size_t)m);
     std::vector<int> live((size_t)m);
     for (int i = 0; i < m; ++i) {
@@ -1689,7 +1693,7 @@ static int align_multi_impl(gsdf_ctx* c, const float* pts_dev, int64_t n, float*
     }
     HIP_TRY(hipMemcpyAsync(d_st, h.data(), (size_t)m * sizeof(gsdf_align_state), hipMemcpyHostToDevice, c->stream));
     if (trace36) HIP_TRY(hipMemsetAsync(d_trace, 0, trace_n * sizeof(float), c->stream));       /* rows beyond a run's end stay zero */
-    if (last36) HIP_TRY(hipMemsetAsync(d_last, 0, (size_t)m * 36 * sizeof(float), c->stream));
+    if (last36) HIP_TRY(hipMemsetAsync(d_last, 0, (size_t)m * row * sizeof(float), c->stream));
     const float conv_sq = conv_threshold * conv_threshold;                 /* RigidOptimizer.h:72 */
     int queued = 0, n_live = m;
     while (queued < num_iterations && n_live > 0) {
@@ -1697,7 +1701,7 @@ static int align_multi_impl(gsdf_ctx* c, const float* pts_dev, int64_t n, float*
         HIP_TRY(hipMemcpyAsync(d_live, live.data(), (size_t)n_live * sizeof(int), hipMemcpyHostToDevice, c->stream));
         for (int k = 0; k < batch; ++k)
             gsdf_launch_align_pass_multi(c->stream, c->tab, c->voxel_size, c->voxel_size_inv, pts_dev, n, d_st, d_part, d_live, n_live,
-                                         conv_sq, damping, num_iterations, d_trace, d_last);
+                                         conv_sq, damping, num_iterations, d_trace, d_last, loss, scale);
         HIP_TRY(hipGetLastError());
         queued += batch;
         HIP_TRY(hipMemcpyAsync(h.data(), d_st, (size_t)m * sizeof(gsdf_align_state), hipMemcpyDeviceToHost, c->stream));
@@ -1708,7 +1712,7 @@ static int align_multi_impl(gsdf_ctx* c, const float* pts_dev, int64_t n, float*
         n_live = kept;
     }
     if (trace36) HIP_TRY(hipMemcpyAsync(trace36, d_trace, trace_n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (last36) HIP_TRY(hipMemcpyAsync(last36, d_last, (size_t)m * 36 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (last36) HIP_TRY(hipMemcpyAsync(last36, d_last, (size_t)m * row * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (trace36 || last36) HIP_TRY(hipStreamSynchronize(c->stream));
     for (int i = 0; i < m; ++i) {
         std::memcpy(poses7 + 7 * i, h[i].pose7, sizeof(h[i].pose7));
@@ -1726,10 +1730,10 @@ static int align_multi_check(gsdf_ctx* c, const float* pts, int64_t n, const flo
 }
 
 /* num_iterations == 0, per run as the single call: nothing executed */
-static int align_multi_none(int m, int* converged, int* passes, float* last36) {
+static int align_multi_none(int m, int* converged, int* passes, float* last36, size_t row = 36) {
     std::fill(converged, converged + m, 0);
     std::fill(passes, passes + m, 0);
-    if (last36) std::fill(last36, last36 + (size_t)m * 36, 0.f);
+    if (last36) std::fill(last36, last36 + (size_t)m * row, 0.f);
     return GSDF_OK;
 }
 
@@ -1837,6 +1841,126 @@ int gsdf_align_best(int m, const int* converged, const int* passes, const float*
     }
     *best = pick;
     return GSDF_OK;
+}
+
+/* ---- the robust registration: the four entries above with a loss's weight on every term (gsdf_align_loss.h) ---- */
+int gsdf_align_loss_weight(int loss, float scale, float phi, float* w) {
+    if (!w || !gsdf_align_loss_valid(loss, scale)) return fail(GSDF_ERR_INVALID, "gsdf_align_loss_weight: bad loss, scale or a null w");
+    *w = gsdf_align_weight(loss, scale, phi);
+    return GSDF_OK;
+}
+
+static int align_loss_check(int loss, float scale) {
+    if (loss < 0 || loss > 4) return fail(GSDF_ERR_INVALID, "gsdf_align_points_robust: loss outside 0 .. 4");
+    if (!gsdf_align_loss_valid(loss, scale)) return fail(GSDF_ERR_INVALID, "gsdf_align_points_robust: the scale is not finite and > 0");
+    return GSDF_OK;
+}
+
+int gsdf_align_points_robust_dev(gsdf_ctx* c, const float* pts_dev, int64_t n, float pose7[7], int num_iterations, float conv_threshold,
+                                 float damping, int loss, float scale, int* converged, int* passes, float* trace38) {
+    GSDF_FLUSH(c);
+    if (int rc = align_points_check(c, pts_dev, n, pose7, num_iterations, converged, passes)) return rc;
+    if (int rc = align_loss_check(loss, scale)) return rc;
+    *converged = 0; *passes = 0;
+    if (num_iterations == 0) return GSDF_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    return align_points_impl(c, pts_dev, n, pose7, num_iterations, conv_threshold, damping, converged, passes, trace38, loss, scale);
+}
+
+int gsdf_align_points_robust(gsdf_ctx* c, const float* pts_host, int64_t n, float pose7[7], int num_iterations, float conv_threshold,
+                             float damping, int loss, float scale, int* converged, int* passes, float* trace38) {
+    GSDF_FLUSH(c);
+    if (int rc = align_points_check(c, pts_host, n, pose7, num_iterations, converged, passes)) return rc;
+    if (int rc = align_loss_check(loss, scale)) return rc;
+    *converged = 0; *passes = 0;
+    if (num_iterations == 0) return GSDF_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    gsdf_dev<void> big;
+    float* d = nullptr;
+    if (int rc = batch_scratch(c, (size_t)n * 3 * sizeof(float), big, (void**)&d)) return rc;
+    if (n > 0) HIP_TRY(hipMemcpyAsync(d, pts_host, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    return align_points_impl(c, d, n, pose7, num_iterations, conv_threshold, damping, converged, passes, trace38, loss, scale);
+}
+
+int gsdf_align_points_multi_robust_dev(gsdf_ctx* c, const float* pts_dev, int64_t n, float* poses7, int m, int num_iterations,
+                                       float conv_threshold, float damping, int loss, float scale, int* converged, int* passes,
+                                       float* last38, float* trace38) {
+    GSDF_FLUSH(c);
+    if (int rc = align_multi_check(c, pts_dev, n, poses7, m, num_iterations, converged, passes)) return rc;
+    if (int rc = align_loss_check(loss, scale)) return rc;
+    if (num_iterations == 0) return align_multi_none(m, converged, passes, last38, 38);
+    HIP_TRY(hipSetDevice(c->device));
+    return align_multi_impl(c, pts_dev, n, poses7, m, num_iterations, conv_threshold, damping, converged, passes, last38, trace38, loss,
+                            scale);
+}
+
+int gsdf_align_points_multi_robust(gsdf_ctx* c, const float* pts_host, int64_t n, float* poses7, int m, int num_iterations,
+                                   float conv_threshold, float damping, int loss, float scale, int* converged, int* passes,
+                                   float* last38, float* trace38) {
+    GSDF_FLUSH(c);
+    if (int rc = align_multi_check(c, pts_host, n, poses7, m, num_iterations, converged, passes)) return rc;
+    if (int rc = align_loss_check(loss, scale)) return rc;
+    if (num_iterations == 0) return align_multi_none(m, converged, passes, last38, 38);
+    HIP_TRY(hipSetDevice(c->device));
+    gsdf_dev<void> big;
+    float* d = nullptr;
+    if (int rc = batch_scratch(c, (size_t)n * 3 * sizeof(float), big, (void**)&d)) return rc;
+    if (n > 0) HIP_TRY(hipMemcpyAsync(d, pts_host, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    return align_multi_impl(c, d, n, poses7, m, num_iterations, conv_threshold, damping, converged, passes, last38, trace38, loss, scale);
+}
+
+/* host only: the run with the smallest E / wsum among the eligible ones */
+int gsdf_align_best_robust(int m, const int* converged, const int* passes, const float* last38, float min_wsum, int require_converged,
+                           int* best) {
+    if (m < 1 || !converged || !passes || !last38 || !best) return fail(GSDF_ERR_INVALID, "gsdf_align_best_robust: bad argument");
+    int pick = -1;
+    double score = 0.0;
+    for (int h = 0; h < m; ++h) {
+        const float E = last38[38 * (size_t)h], wsum = last38[38 * (size_t)h + 36];
+        if (passes[h] <= 0 || (require_converged && !converged[h])) continue;
+        if (!(wsum >= min_wsum) || !(wsum > 0.f) || !std::isfinite(E)) continue;   /* no weight: E / wsum is no score */
+        const double s = (double)E / (double)wsum;
+        if (pick < 0 || s < score) { pick = h; score = s; }
+    }
+    *best = pick;
+    return GSDF_OK;
+}
+
+/* what a pass from pose7 sees per point; pts_dev == nullptr: the points are staged from pts_host */
+static int align_residuals_impl(gsdf_ctx* c, const float* pts_host, const float* pts_dev, int64_t n, const float* pose7, float* phi_out,
+                                float* w_out) {
+    if (!c || !pose7) return fail(GSDF_ERR_INVALID, "gsdf_align_residuals: null argument");
+    if (n < 0) return fail(GSDF_ERR_INVALID, "gsdf_align_residuals: negative n");
+    if (n > 0 && ((!pts_host && !pts_dev) || !phi_out || !w_out)) return fail(GSDF_ERR_INVALID, "gsdf_align_residuals: null points or outputs");
+    if (c->map_type == GSDF_MAP_BASE)
+        return fail(GSDF_ERR_INVALID, "gsdf_align_residuals: not available on a base-sdf context (it reads the stored gradient)");
+    if (n == 0) return GSDF_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t un = (size_t)n;
+    gsdf_dev<void> big;
+    float* d = nullptr;
+    if (int rc = batch_scratch(c, un * (pts_dev ? 2 : 5) * sizeof(float), big, (void**)&d)) return rc;
+    float *dphi = d, *dw = d + un;
+    if (!pts_dev) {
+        HIP_TRY(hipMemcpyAsync(d + 2 * un, pts_host, un * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        pts_dev = d + 2 * un;
+    }
+    gsdf_launch_align_residuals(c->stream, c->tab, c->voxel_size, c->voxel_size_inv, pts_dev, n, pose7, dphi, dw);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(phi_out, dphi, un * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(w_out, dw, un * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return GSDF_OK;
+}
+
+int gsdf_align_residuals(gsdf_ctx* c, const float* pts_host, int64_t n, const float pose7[7], float* phi_out, float* w_out) {
+    GSDF_FLUSH(c);
+    return align_residuals_impl(c, pts_host, nullptr, n, pose7, phi_out, w_out);
+}
+
+int gsdf_align_residuals_dev(gsdf_ctx* c, const float* pts_dev, int64_t n, const float pose7[7], float* phi_out, float* w_out) {
+    GSDF_FLUSH(c);
+    return align_residuals_impl(c, nullptr, pts_dev, n, pose7, phi_out, w_out);
 }
 
 /* MapGradPixelSdf::extract_pc's rows (MapGradPixelSdf.cpp:182-195) into `out_dev` (rows_dev != nullptr) or `rows_host` */

@@ -195,16 +195,24 @@ struct gsdf_align_state {
     int done, converged, passes;
 };
 int  gsdf_align_grid(long long n);
+/* loss < 0: the plain pair above, trace rows of 36 floats.  loss in 0..4 (gsdf_align_loss.h): the robust pair k_align_pass_robust /
+ * k_align_head_robust -- every term times the weight of its point, GSDF_ALIGN_NSUM_ROBUST sums per row (the 29, the weight sum,
+ * the number of points of weight > 0) and trace rows of 38 floats.  The same for the _multi launch below. */
+#define GSDF_ALIGN_NSUM_ROBUST 31
 void gsdf_launch_align_pass(hipStream_t s, gsdf_table tab, float vs, float inv_vs, const float* pts, long long n,
                             gsdf_align_state* st, double* part /* GSDF_ALIGN_MAXBLK x GSDF_ALIGN_ROW */, float conv_sq, float damping,
-                            int max_passes, float* trace /* nullable: max_passes x 36 */);
+                            int max_passes, float* trace /* nullable: max_passes x 36 (38) */, int loss = -1, float scale = 0.f);
 /* The same for the n_live runs live[0..n_live) of a batch of m starts, in one pass launch of gsdf_align_grid(n) x n_live
  * workgroups and one head launch of n_live workgroups (k_align_pass_multi, k_align_head_multi: the bodies of the pair above, so
  * run h's bytes are those of a single run from st[h]).  st[m]; part[m][gsdf_align_grid(n)][GSDF_ALIGN_ROW]; trace (nullable)
  * [m][max_passes][36]; last (nullable) [m][36] = the row of run h's latest pass.  A run whose done is set is skipped. */
 void gsdf_launch_align_pass_multi(hipStream_t s, gsdf_table tab, float vs, float inv_vs, const float* pts, long long n,
                                   gsdf_align_state* st, double* part, const int* live, int n_live, float conv_sq, float damping,
-                                  int max_passes, float* trace, float* last);
+                                  int max_passes, float* trace, float* last, int loss = -1, float scale = 0.f);
+/* What a pass from pose7 sees per point (k_align_residuals): phi_out[i], w_out[i] = the distance and the voxel's weight at
+ * R x_i + t, both 0 for a missing voxel or a point that is not finite after the transform.  n device floats each. */
+void gsdf_launch_align_residuals(hipStream_t s, gsdf_table tab, float vs, float inv_vs, const float* pts, long long n,
+                                 const float pose7[7], float* phi_out, float* w_out);
 /* The surface cloud (MapGradPixelSdf::extract_pc, MapGradPixelSdf.cpp:182-195): flag = packed key and slot of every voxel that
  * passes the gates, appended through `counter` (keys == nullptr: count only); rows = the 6-float rows from the slots in sorted
  * key order (the caller sorts the pairs with gsdf_sort_pairs_u64) */

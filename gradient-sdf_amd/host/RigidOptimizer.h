@@ -35,6 +35,8 @@ class RigidPointOptimizer : public RigidOptimizer {
     int last_passes_ = 0;
     std::vector<int> multi_converged_, multi_passes_;
     std::vector<float> multi_poses_;
+    int loss_ = 0;                               /* L2: the plain entries */
+    float loss_scale_ = 0.f;
 public:
     RigidPointOptimizer(Sdf* tSDF) : RigidOptimizer(tSDF) {}
     RigidPointOptimizer(int num_iterations, float conv_threshold, float damping, Sdf* tSDF)
@@ -56,6 +58,18 @@ public:
     const std::vector<int>& multi_passes() const { return multi_passes_; }
     const std::vector<float>& multi_poses() const { return multi_poses_; }
     int last_passes() const { return last_passes_; }
+    /* The loss of optimize_points / optimize_points_multi: 0 L2 (the default: the plain gsdf_align_points entries), 1 CAUCHY,
+     * 2 HUBER, 3 TUKEY, 4 TRUNC_L2 (ps_optimizer/loss.h:41-48) at `scale` metres -- gsdf_align_points_robust, and for the multi
+     * call the pick of gsdf_align_best_robust, where min_count is the floor of the weight sum.  A loss outside 0..4, or a scale
+     * that is not finite and > 0 with a loss other than L2, throws std::invalid_argument and changes nothing.  optimize() and
+     * optimize_sampled() are not affected. */
+    void set_loss(int loss, float scale);
+    int loss() const { return loss_; }
+    float loss_scale() const { return loss_scale_; }
+    /* The distance and the voxel weight each of the n points meets under `pose` (source -> map), as a pass from that pose sees
+     * them (gsdf_align_residuals): phi and w are resized to n; both are 0 where the voxel is missing.  With pose() after a
+     * robust run, |phi| against the loss's scale splits the cloud into what registered and what moved. */
+    void residuals(const float* xyz, size_t n, SE3 pose, std::vector<float>& phi, std::vector<float>& w);
 };
 
 #endif

@@ -568,6 +568,67 @@ int gsdf_align_starts(const float center7[7], const float pivot[3], float rot_st
 int gsdf_align_best(int m, const int* converged, const int* passes, const float* last36, int64_t min_count,
                     int require_converged, int* best);
 
+/* ROBUST REGISTRATION.  gsdf_align_points minimises the plain sum of squares of RigidPointOptimizer.cpp:76-81: right for a depth
+ * frame against the map it was tracked on, wrong for two sessions of a scene in which something moved or that overlap in part --
+ * the points that do not belong pull the pose.  The entries below multiply every term of a point by the weight a robust loss
+ * gives its distance (iteratively reweighted least squares with a constant scale).  The loss family is the reference's
+ * ps_optimizer/loss.h:41-48 and the integers are those of gsdf_ba_set_loss.
+ *
+ * The weight of one point.  Host only: no context, no GPU; it is the inline function the kernel calls (csrc/gsdf_align_loss.h).
+ * All float, no contraction, correctly rounded divisions.  With a = |phi|, k = scale, r = phi / k, rr = r * r:
+ *     0 L2        1 (scale ignored)
+ *     1 CAUCHY    1 / (1 + rr)
+ *     2 HUBER     a <= k ? 1 : k / a
+ *     3 TUKEY     a < k ? (1 - rr) * (1 - rr) : 0
+ *     4 TRUNC_L2  a < k ? 1 : 0
+ * GSDF_ERR_INVALID: loss outside 0..4, a NULL w, and for loss != 0 a scale that is not finite or not > 0. */
+int gsdf_align_loss_weight(int loss, float scale, float phi, float* w);
+
+/* gsdf_align_points / _dev / _multi / _multi_dev with a loss.  Per point everything up to the map values (w0, phi, g) is the plain
+ * pass; where w0 > 0, with one float operation per step: rw = the weight above of phi, wphi = rw * phi, wJ[a] = rw * J[a]; the
+ * terms are wphi * phi, wphi * J[a] and wJ[a] * J[b] (a <= b); the count is raised by 1 as before; two more sums: wsum += rw and
+ * n_in += 1 where rw > 0.  The 31 sums are widened, ordered and rounded exactly as the 29 of the plain pass.  Head, stop rule, pose
+ * update, batching and scratch are the plain call's (the partial rows had the room).
+ * The trace rows are 38 floats wide: [0..35] as in gsdf_align_points with the weighted E, g and H, [36] = wsum, [37] = n_in.
+ * trace38: num_iterations x 38 (m x num_iterations x 38 for the multi entries), last38: m x 38; both nullable.
+ * With loss = 0 every output is equal in BYTES to the plain entry's for the same call (pose, flags, passes, floats [0..35] of
+ * every row), and [36] == [37] == [28].  Run h of a multi call is equal in bytes to the single robust call from poses7[h].
+ * GSDF_ERR_INVALID with every output untouched: what the plain entry refuses (a base-sdf context included), a loss outside 0..4
+ * and, for loss != 0, a scale that is not finite or not > 0.  The context's persistent pose, frame log and gsdf_stats are
+ * neither read nor written.  Not built: a normal-compatibility gate, an annealed or automatic scale, base maps, multi-GPU. */
+int gsdf_align_points_robust(gsdf_ctx* c, const float* pts_host, int64_t n, float pose7[7],
+                             int num_iterations, float conv_threshold, float damping, int loss, float scale,
+                             int* converged, int* passes, float* trace38 /* nullable */);
+int gsdf_align_points_robust_dev(gsdf_ctx* c, const float* pts_dev, int64_t n, float pose7[7],
+                                 int num_iterations, float conv_threshold, float damping, int loss, float scale,
+                                 int* converged, int* passes, float* trace38 /* nullable */);
+int gsdf_align_points_multi_robust(gsdf_ctx* c, const float* pts_host, int64_t n, float* poses7 /* m x 7, in/out */, int m,
+                                   int num_iterations, float conv_threshold, float damping, int loss, float scale,
+                                   int* converged /* m */, int* passes /* m */,
+                                   float* last38 /* m x 38, nullable */, float* trace38 /* m x num_iterations x 38, nullable */);
+int gsdf_align_points_multi_robust_dev(gsdf_ctx* c, const float* pts_dev, int64_t n, float* poses7 /* m x 7, in/out */, int m,
+                                       int num_iterations, float conv_threshold, float damping, int loss, float scale,
+                                       int* converged /* m */, int* passes /* m */,
+                                       float* last38 /* m x 38, nullable */, float* trace38 /* m x num_iterations x 38, nullable */);
+
+/* gsdf_align_best for the runs of gsdf_align_points_multi_robust.  Host only.  Run h is eligible if passes[h] > 0, converged[h]
+ * (unless !require_converged), wsum = last38[h][36] >= min_wsum and > 0, and E = last38[h][0] is finite; its score is (double)E /
+ * (double)wsum, the weighted mean squared distance.  *best = the eligible run of the smallest score, the lowest index on a tie,
+ * or -1 (still GSDF_OK) if none is eligible.  GSDF_ERR_INVALID: m < 1 or a NULL argument. */
+int gsdf_align_best_robust(int m, const int* converged, const int* passes, const float* last38, float min_wsum,
+                           int require_converged, int* best);
+
+/* What a pass from pose7 (tx ty tz qx qy qz qw, source -> map) sees per point: p = R x + t exactly as the pass forms it, then the
+ * map values at p as gsdf_query returns them.  w_out[i] = the voxel's weight, 0 for a missing voxel or a point that is not finite
+ * after the transform; phi_out[i] = the distance, 0 where w_out[i] == 0.  With the pose a registration returned, |phi_out| splits
+ * the cloud into the part that registered and the part that moved.  phi_out and w_out are HOST buffers of n floats in both
+ * variants; the _dev variant reads n x 3 floats of device memory in place.  One lane per point (k_align_residuals).
+ * n == 0: nothing is written (the pointers may be NULL).  GSDF_ERR_INVALID: a NULL c / pose7, n < 0, NULL points or outputs with
+ * n > 0, a base-sdf context.  Synchronous; a waiting pipelined fusion is launched first; the table is only read, and the
+ * persistent pose, the frame log and gsdf_stats are untouched. */
+int gsdf_align_residuals(gsdf_ctx* c, const float* pts_host, int64_t n, const float pose7[7], float* phi_out, float* w_out);
+int gsdf_align_residuals_dev(gsdf_ctx* c, const float* pts_dev, int64_t n, const float pose7[7], float* phi_out, float* w_out);
+
 /* MapGradPixelSdf::extract_pc (MapGradPixelSdf.cpp:177-195) in memory instead of an ASCII PLY: one row x y z nx ny nz per voxel
  * with weight >= 5 (:184) and |dist * 1.2 g^| < voxel_size / 2 on every axis (:186-188), point = vox2float(idx) - dist * 1.2 g^
  * (:191), normal = -1.2 g^ (:192), all in float; g^ the normalised stored gradient sum.  The reference's row order is its hash

@@ -8,7 +8,8 @@ final E / hits, the recovered pose's error, the wall time of the call (median of
 time of one batch of 5 pass + head pairs divided by 5 (conv_threshold = 0, so all five run) next to the event time of
 k_track_pass's launches on map A for a frame of the stream.  One JSON line, also written to profiles/align_points.json (or --out).
 --merge goes on to the merge under the recovered pose instead (merge_main): profiles/merge_posed.json.
---multi measures the multi-start registration instead (multi_main): profiles/align_multi.json."""
+--multi measures the multi-start registration instead (multi_main): profiles/align_multi.json.
+--robust measures the registration with a robust loss beside the plain one (robust_main): profiles/align_robust.json."""
 import argparse, json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -214,20 +215,132 @@ def multi_main(args):
     return 0
 
 
+def robust_main(args):
+    """--robust: the registration with a robust loss (gsdf_align_points_robust, Tukey at 2 cm) beside the plain one, on two scenes.
+    (1) The demonstration scene of tests/test_gpu_align_robust.py: 320x240 spheres, 1 cm voxels, trunc 10, sessions A (frames 0..7)
+    and B (frames 4..11), the third sphere of B moved by (0.04, -0.02, 0.012) m.  (2) The bench-stream pair of the other modes with
+    a block of B's cloud displaced: the points inside a 0.5 m cube about the cloud's centroid are shifted by (0.05, -0.03, 0.02) m.
+    Per scene: the pose errors of the plain and of the robust run from the identity, and from gsdf_align_residuals under either
+    pose the hit points with |phi| >= 2 cm, and how many of them belong to the part that moved.  On the bench pair also the
+    HIP-event time of a robust pass + head pair beside the plain pair (a 5-pair batch with conv_threshold = 0, divided by 5, median
+    of --reps) and the wall time of a 27-start robust call beside the plain 27-start call, all in this process.  One JSON line,
+    also written to profiles/align_robust.json (or --out)."""
+    import __graft_entry__ as graft
+    import align_points_ref as ref
+    pkg = graft.package()
+    B = pkg.binding
+    LOSS, SCALE = B.LOSS_TUKEY, np.float32(0.02)
+
+    def errors(pose, Rd, td):
+        Rg = quat_to_R(pose[3:])
+        return (round(float(np.rad2deg(np.arccos(np.clip((np.trace(Rg.T @ Rd) - 1) / 2, -1, 1)))), 4),
+                round(1e3 * float(np.abs(pose[:3].astype(np.float64) - td).max()), 3))
+
+    def compare(a, dev, npts, Rd, td, moved):
+        """the plain and the robust run from the identity; `moved`: bool [npts], the points that do not belong"""
+        res = {}
+        for name, run in (("l2", lambda: a.align_points_dev(dev, npts, ref.IDENTITY)),
+                          ("tukey_2cm", lambda: a.align_points_robust_dev(dev, npts, ref.IDENTITY, LOSS, SCALE))):
+            conv, pose, passes, trace = run()
+            ang, terr = errors(pose, Rd, td)
+            phi, w = a.align_residuals_dev(dev, npts, pose)
+            off = (w > 0) & (np.abs(phi) >= SCALE)
+            res[name] = {"converged": bool(conv), "passes": int(passes), "rotation_error_deg": ang, "translation_error_mm": terr,
+                         "hits": int((w > 0).sum()), "hits_2cm_or_more_off": int(off.sum()), "of_which_moved": int((off & moved).sum()),
+                         "inliers": int(((w > 0) & ~off).sum())}
+            if name != "l2":
+                res[name]["wsum_last_pass"] = float(trace[-1, 36]) if passes else None
+                res[name]["n_in_last_pass"] = int(trace[-1, 37]) if passes else None
+        return res
+
+    # (1) the demonstration scene
+    W, H = 320, 240
+    kw = dict(n_frames=12, seed=1, step_deg=0.5)
+    sa, sb = pkg.synth.Sequence("spheres", W, H, **kw), pkg.synth.Sequence("spheres", W, H, **kw)
+    sb.spheres = np.array(sb.spheres, np.float64).copy()
+    sb.spheres[2, :3] += (0.04, -0.02, 0.012)
+    vs = np.float32(0.01); T = np.float32(10) * vs
+    a = pkg.GradSdf(vs, T, W, H, sa.K, capacity_log2=21)
+    b = pkg.GradSdf(vs, T, W, H, sa.K, capacity_log2=21)
+    for i in range(8):
+        a.update(*sa.frame(i))
+    for i in range(4, 12):
+        b.update(*sb.frame(i))
+    cloud = b.surface_cloud()[:, :3]
+    c, r = sb.spheres[2, :3], float(sb.spheres[2, 3])
+    on_moved = np.abs(np.linalg.norm(cloud.astype(np.float64) - c, axis=1) - r) < 2.0 * float(vs)
+    src, Rd, td = ref.displace(cloud)
+    demo = {"scene": "spheres %dx%d, A = frames 0..7, B = frames 4..11 with sphere 2 moved by (0.04, -0.02, 0.012) m, voxel %.3g m" % (W, H, float(vs)),
+            "points": int(len(src)), "points_on_the_moved_sphere": int(on_moved.sum())}
+    demo.update(compare(a, a.upload(src), len(src), Rd, td, on_moved))
+    a.close(); b.close()
+
+    # (2) the bench-stream pair with a block of B's cloud displaced
+    W, H, n = 640, 480, args.frames
+    seq = pkg.synth.Sequence("tum", W, H, n_frames=n, seed=0)
+    a = pkg.GradSdf(vs, T, W, H, seq.K, capacity_log2=22)
+    b = pkg.GradSdf(vs, T, W, H, seq.K, capacity_log2=22)
+    frames = [seq.frame(i) for i in range(n)]
+    for i in range(n // 2):
+        a.update(*frames[i])
+    for i in range(n // 2, n):
+        b.update(*frames[i])
+    cloud = b.surface_cloud()[:, :3].copy()
+    npts = len(cloud)
+    block = (np.abs(cloud.astype(np.float64) - cloud.astype(np.float64).mean(axis=0)) < 0.25).all(axis=1)
+    cloud[block] += np.array([0.05, -0.03, 0.02], np.float32)
+    src, Rd, td = ref.displace(cloud)
+    dev = a.upload(src)
+    bench = {"scene": "S-tum %dx%d, %d frames (A = first half, B = second half), voxel %.3g m; B's points within 0.25 m of the centroid per axis moved by (0.05, -0.03, 0.02) m" % (W, H, n, float(vs)),
+             "points": int(npts), "points_in_the_moved_block": int(block.sum())}
+    bench.update(compare(a, dev, npts, Rd, td, block))
+    # timings, the plain kernels and the robust ones side by side in this process
+    starts = B.align_starts(ref.IDENTITY, src.astype(np.float64).mean(axis=0), 0.0, 0, 0.1, 1)
+    pair_l2, pair_rb, call_l2, call_rb, multi_l2, multi_rb = [], [], [], [], [], []
+    a.align_points_dev(dev, npts, ref.IDENTITY); a.align_points_robust_dev(dev, npts, ref.IDENTITY, LOSS, SCALE)       # warm
+    a.align_points_multi_dev(dev, npts, starts); a.align_points_multi_robust_dev(dev, npts, starts, LOSS, SCALE)
+    for _ in range(args.reps):
+        a.timer_start(); a.align_points_dev(dev, npts, ref.IDENTITY, iters=5, conv=0.0); pair_l2.append(a.timer_stop_ms() / 5)
+        a.timer_start(); a.align_points_robust_dev(dev, npts, ref.IDENTITY, LOSS, SCALE, iters=5, conv=0.0); pair_rb.append(a.timer_stop_ms() / 5)
+        t0 = time.perf_counter(); a.align_points_dev(dev, npts, ref.IDENTITY, conv=0.0); call_l2.append(time.perf_counter() - t0)
+        t0 = time.perf_counter(); a.align_points_robust_dev(dev, npts, ref.IDENTITY, LOSS, SCALE, conv=0.0); call_rb.append(time.perf_counter() - t0)
+        t0 = time.perf_counter(); a.align_points_multi_dev(dev, npts, starts, conv=0.0); multi_l2.append(time.perf_counter() - t0)
+        t0 = time.perf_counter(); a.align_points_multi_robust_dev(dev, npts, starts, LOSS, SCALE, conv=0.0); multi_rb.append(time.perf_counter() - t0)
+    t0 = time.perf_counter(); a.align_residuals_dev(dev, npts, ref.IDENTITY); t_res = time.perf_counter() - t0
+    med = lambda v, k: round(float(np.median(v)) * k, 3)                   # noqa: E731
+    bench["timing"] = {"note": "conv_threshold = 0: every call runs all its passes, so both losses do the same number of launches",
+                       "pass_plus_head_pair_event_us": {"l2": med(pair_l2, 1e3), "tukey_2cm": med(pair_rb, 1e3)},
+                       "call_25_passes_wall_ms": {"l2": med(call_l2, 1e3), "tukey_2cm": med(call_rb, 1e3)},
+                       "call_27_starts_25_passes_wall_ms": {"l2": med(multi_l2, 1e3), "tukey_2cm": med(multi_rb, 1e3)},
+                       "residuals_call_wall_ms": round(t_res * 1e3, 3),
+                       "workgroups": int(min(max((npts + 255) // 256, 1), 512)), "reps": args.reps}
+    a.close(); b.close()
+    out = {"loss": "TUKEY", "scale_m": float(SCALE), "demonstration": demo, "bench_pair": bench}
+    line = json.dumps(out)
+    print(line)
+    with open(args.out, "w") as f:
+        f.write(line + "\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--merge", action="store_true", help="also merge B into A under the recovered pose (gsdf_merge_from_posed); writes profiles/merge_posed.json")
     ap.add_argument("--multi", action="store_true", help="multi-start registration (gsdf_align_points_multi) against sequential single calls, and the basin sweep; writes profiles/align_multi.json")
+    ap.add_argument("--robust", action="store_true", help="robust registration (gsdf_align_points_robust, Tukey at 2 cm) beside the plain one on a scene with a moved object, residual counts and timings; writes profiles/align_robust.json")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "merge_posed.json" if args.merge else "align_multi.json" if args.multi else "align_points.json")
+        args.out = os.path.join(ROOT, "profiles", "merge_posed.json" if args.merge else "align_multi.json" if args.multi else
+                                "align_robust.json" if args.robust else "align_points.json")
     if args.merge:
         return merge_main(args)
     if args.multi:
         return multi_main(args)
+    if args.robust:
+        return robust_main(args)
     import __graft_entry__ as graft
     import align_points_ref as ref
     pkg = graft.package()
