@@ -12,3 +12,4 @@ The directory name contains a hyphen (task contract); import it through
 """
 from . import binding, parallel, synth  # noqa: F401
 from .binding import MAP_BASE, MAP_GRAD, MESH_KEEP_LARGEST, GradSdf, GsdfError  # noqa: F401
+from .binding import SEL_ADD, SEL_INTERSECT, SEL_REPLACE, SEL_SUBTRACT  # noqa: F401

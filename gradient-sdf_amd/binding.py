@@ -25,6 +25,7 @@ TEST_LIB_PATH = os.environ.get("GSDF_TEST_LIB", os.path.join(CSRC, "libgsdf_test
 GSDF_OK, ERR_TABLE_FULL, ERR_KEY_RANGE, ERR_INVALID, ERR_HIP, ERR_NO_DEVICE = 0, 1, 2, 3, 4, 5
 MAP_GRAD, MAP_BASE = 0, 1                                     # gsdf_set_map_type (include/gsdf.h)
 MESH_KEEP_LARGEST = -1                                        # gsdf_extract_mesh_indexed_filtered's min_faces (GSDF_MESH_KEEP_LARGEST)
+SEL_REPLACE, SEL_ADD, SEL_INTERSECT, SEL_SUBTRACT = 0, 1, 2, 3   # the op of the gsdf_select_* entries (GSDF_SEL_*)
 
 
 class GsdfError(RuntimeError):
@@ -181,6 +182,17 @@ def load(path=None):
         "gsdf_align_residuals_dev": (C.c_int, [vp, vp, C.c_int64, fp, fp, fp]),
         "gsdf_surface_cloud": (C.c_int, [vp, fp, C.c_int64, i64p]),
         "gsdf_surface_cloud_dev": (C.c_int, [vp, vp, C.c_int64, i64p]),
+        "gsdf_select_box": (C.c_int, [vp, fp, fp, C.c_int, i64p]),
+        "gsdf_select_weight": (C.c_int, [vp, C.c_float, C.c_float, C.c_int, i64p]),
+        "gsdf_select_points": (C.c_int, [vp, fp, C.c_int64, fp, C.c_float, C.c_int, i64p]),
+        "gsdf_select_points_dev": (C.c_int, [vp, vp, C.c_int64, fp, C.c_float, C.c_int, i64p]),
+        "gsdf_select_invert": (C.c_int, [vp, i64p]),
+        "gsdf_select_clear": (C.c_int, [vp]),
+        "gsdf_select_count": (C.c_int, [vp, i64p, i64p]),
+        "gsdf_select_export": (C.c_int, [vp, i32p, fp, C.c_int64, i64p, C.c_int]),
+        "gsdf_select_export_raw_dev": (C.c_int, [vp, vp, vp, C.c_int64, i64p]),
+        "gsdf_erase_selected": (C.c_int, [vp, i64p, i64p]),
+        "gsdf_compact": (C.c_int, [vp, C.c_int, i64p]),
         "gsdf_block_keys_dev": (C.c_int, [vp, vp, C.c_int64, C.POINTER(C.c_int64)]),
         "gsdf_pack_blocks_dev": (C.c_int, [vp, vp, C.c_int64, vp]),
         "gsdf_unpack_blocks_dev": (C.c_int, [vp, vp, C.c_int64, vp]),
@@ -247,6 +259,8 @@ ABI_SYMBOLS = [
     "gsdf_align_points_multi", "gsdf_align_points_multi_dev", "gsdf_align_starts", "gsdf_align_best",
     "gsdf_align_loss_weight", "gsdf_align_points_robust", "gsdf_align_points_robust_dev", "gsdf_align_points_multi_robust",
     "gsdf_align_points_multi_robust_dev", "gsdf_align_best_robust", "gsdf_align_residuals", "gsdf_align_residuals_dev",
+    "gsdf_select_box", "gsdf_select_weight", "gsdf_select_points", "gsdf_select_points_dev", "gsdf_select_invert", "gsdf_select_clear",
+    "gsdf_select_count", "gsdf_select_export", "gsdf_select_export_raw_dev", "gsdf_erase_selected", "gsdf_compact",
     "gsdf_raycast", "gsdf_raycast_dev", "gsdf_raycast_counters", "gsdf_extract_mesh",
     "gsdf_extract_mesh_indexed", "gsdf_mesh_components", "gsdf_extract_mesh_indexed_filtered", "gsdf_gradient_angles", "gsdf_gradient_stats",
     "gsdf_dev_alloc", "gsdf_dev_free", "gsdf_dev_upload", "gsdf_dev_download", "gsdf_timer_start", "gsdf_timer_stop_ms",
@@ -939,6 +953,95 @@ class GradSdf:
         p = rows_dev if isinstance(rows_dev, C.c_void_p) or rows_dev is None else C.c_void_p(int(rows_dev))
         self._chk(self.L.gsdf_surface_cloud_dev(self.h, p, int(max_n), C.byref(n)))
         return n.value
+
+    # -- removing voxels: the selection, erase, compact (include/gsdf.h, "REMOVING VOXELS") ---------------
+    def select_box(self, lo, hi, op=SEL_REPLACE):
+        """gsdf_select_box: voxels whose centre lies in the closed box [lo, hi]; returns the members that exist"""
+        lo, hi = _f32(lo).reshape(3).copy(), _f32(hi).reshape(3).copy()
+        n = C.c_int64(0)
+        self._chk(self.L.gsdf_select_box(self.h, _fp(lo), _fp(hi), int(op), C.byref(n)))
+        return n.value
+
+    def select_weight(self, w_min, w_max, op=SEL_REPLACE):
+        """gsdf_select_weight: voxels with w_min <= weight < w_max"""
+        n = C.c_int64(0)
+        self._chk(self.L.gsdf_select_weight(self.h, np.float32(w_min), np.float32(w_max), int(op), C.byref(n)))
+        return n.value
+
+    def select_points(self, pts, radius, pose7=None, op=SEL_REPLACE):
+        """gsdf_select_points: voxels whose centre lies within `radius` of some point (pose7: the points are moved by it first)"""
+        p = _f32(pts).reshape(-1, 3)
+        q = None if pose7 is None else _f32(pose7).reshape(7).copy()
+        n = C.c_int64(0)
+        self._chk(self.L.gsdf_select_points(self.h, _fp(p) if len(p) else None, len(p), None if q is None else _fp(q),
+                                            np.float32(radius), int(op), C.byref(n)))
+        return n.value
+
+    def select_points_dev(self, pts_dev, n_pts, radius, pose7=None, op=SEL_REPLACE):
+        """gsdf_select_points_dev: the same over n_pts x 3 floats of device memory, read in place"""
+        q = None if pose7 is None else _f32(pose7).reshape(7).copy()
+        p = pts_dev if isinstance(pts_dev, C.c_void_p) else C.c_void_p(int(pts_dev))
+        n = C.c_int64(0)
+        self._chk(self.L.gsdf_select_points_dev(self.h, p, int(n_pts), None if q is None else _fp(q), np.float32(radius), int(op),
+                                                C.byref(n)))
+        return n.value
+
+    def select_invert(self):
+        n = C.c_int64(0)
+        self._chk(self.L.gsdf_select_invert(self.h, C.byref(n)))
+        return n.value
+
+    def select_clear(self):
+        self._chk(self.L.gsdf_select_clear(self.h))
+
+    def select_count(self):
+        """gsdf_select_count: (members that exist, blocks that hold one)"""
+        nv, nb = C.c_int64(0), C.c_int64(0)
+        self._chk(self.L.gsdf_select_count(self.h, C.byref(nv), C.byref(nb)))
+        return nv.value, nb.value
+
+    def select_export(self, raw=False):
+        """gsdf_select_export: keys [n, 3] and payload [n, 5] of the members, in (z, y, x) key order"""
+        n = C.c_int64(0)
+        self._chk(self.L.gsdf_select_export(self.h, None, None, 0, C.byref(n), int(raw)))
+        keys = np.empty((n.value, 3), np.int32)
+        pay = np.empty((n.value, 5), np.float32)
+        if n.value:
+            self._chk(self.L.gsdf_select_export(self.h, keys.ctypes.data_as(C.POINTER(C.c_int32)), _fp(pay), n.value, C.byref(n), int(raw)))
+        return keys, pay
+
+    def select_export_raw_dev(self, keys_ptr, payload_ptr, max_n):
+        """gsdf_select_export_raw_dev: (key, raw sums) of the members into device buffers, unordered; returns their number"""
+        n = C.c_int64(0)
+        self._chk(self.L.gsdf_select_export_raw_dev(self.h, C.c_void_p(keys_ptr), C.c_void_p(payload_ptr), int(max_n), C.byref(n)))
+        return n.value
+
+    def erase_selected(self):
+        """gsdf_erase_selected: (voxels erased, blocks that hold none afterwards)"""
+        nv, nb = C.c_int64(0), C.c_int64(0)
+        self._chk(self.L.gsdf_erase_selected(self.h, C.byref(nv), C.byref(nb)))
+        return nv.value, nb.value
+
+    def compact(self, new_capacity_log2=0):
+        """gsdf_compact: the table rebuilt without its empty blocks (0 keeps the capacity); returns the blocks dropped"""
+        n = C.c_int64(0)
+        self._chk(self.L.gsdf_compact(self.h, int(new_capacity_log2), C.byref(n)))
+        return n.value
+
+    def crop(self, lo, hi):
+        """keep only the voxels whose centre lies in the box: select_box, invert, erase, compact.  Returns the voxels erased."""
+        self.select_box(lo, hi)
+        self.select_invert()
+        nv, _ = self.erase_selected()
+        self.compact()
+        return nv
+
+    def prune(self, min_weight):
+        """drop the voxels of weight below min_weight: select_weight [0, min_weight), erase, compact.  Returns the voxels erased."""
+        self.select_weight(0.0, min_weight)
+        nv, _ = self.erase_selected()
+        self.compact()
+        return nv
 
     def raycast(self, R, t, zmin=0.5, zmax=3.5, W=None, H=None, K=None, normals=True):
         """Voxel-hash raycaster: (depth[H,W] camera z, 0 = no hit; normals[3,H,W] camera frame or None)."""

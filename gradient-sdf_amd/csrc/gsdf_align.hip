@@ -64,8 +64,7 @@ __device__ __forceinline__ void align_pass_body(gsdf_table tab, float vs, float 
     const long long stride = (long long)gridDim.x * GSDF_ALIGN_BLOCK;
     for (long long i = (long long)blockIdx.x * GSDF_ALIGN_BLOCK + threadIdx.x; i < n; i += stride) {
         const gsdf_v3 x = { pts[3 * i], pts[3 * i + 1], pts[3 * i + 2] };
-        const gsdf_v3 Rx = gsdf_matvec(R, x);
-        const gsdf_v3 p = { Rx.x + t.x, Rx.y + t.y, Rx.z + t.z };          /* :70 */
+        const gsdf_v3 p = gsdf_rigid_apply(R, t, x);                       /* :70 */
         /* a point that is not finite never reaches the float -> int conversion of float2vox (the reference would convert it) */
         if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) continue;
         float w0, phi;
@@ -334,8 +333,7 @@ __global__ __launch_bounds__(256) void k_align_residuals(gsdf_table tab, float v
     const long long stride = (long long)gridDim.x * 256;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
         const gsdf_v3 x = { pts[3 * i], pts[3 * i + 1], pts[3 * i + 2] };
-        const gsdf_v3 Rx = gsdf_matvec(R, x);
-        const gsdf_v3 p = { Rx.x + t.x, Rx.y + t.y, Rx.z + t.z };
+        const gsdf_v3 p = gsdf_rigid_apply(R, t, x);
         float w0 = 0.f, phi = 0.f;
         if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
             gsdf_v3 g;

@@ -734,6 +734,7 @@ int gsdf_reset(gsdf_ctx* c) {
     c->color.drop();                                         /* the ColorUpsampler snapshot describes the old map */
     c->grow_forget = true;                                   /* auto-grow's block counts describe the old map (a grown table keeps its size) */
     c->occ_dirty = false;                                    /* the table clear zeroed the filters as well */
+    c->sel_state = GSDF_SEL_NONE;                            /* the selection goes with the map */
     return GSDF_OK;
 }
 

@@ -20,13 +20,18 @@
 #define GSDF_SCRATCH_BYTES (256 * 1024)
 #define GSDF_MX_BUFS 8
 #define GSDF_GROW_MAX_LAG_DEFAULT 8       /* auto-grow: frame entries the host may be ahead of the newest finished block count */
-#define GSDF_PROF_SLOTS 5     /* gsdf_profile: 0 normals, 1 fusion, 2 tracking launches, 3 raycast, 4 tracker (whole optimize) */
+enum { GSDF_SEL_NONE = 0, GSDF_SEL_VALID = 1, GSDF_SEL_LOST = 2 };   /* gsdf_ctx::sel_state */
+#define GSDF_PROF_SLOTS 5    /* gsdf_profile: 0 normals, 1 fusion, 2 tracking launches, 3 raycast, 4 tracker (whole optimize) */
 
 inline thread_local std::string g_gsdf_err;
 
 struct gsdf_ctx;
 int gsdf_flush_pending(gsdf_ctx* c);               /* gsdf_capi.hip: launch the deferred GT-pose fusion, if one waits */
 int gsdf_grow_impl(gsdf_ctx* c, int new_capacity_log2);      /* gsdf_merge.hip: rehash into a larger table */
+/* gsdf_merge.hip: the rebuild behind gsdf_grow and gsdf_compact -- every block (skip_dead: every block that holds a voxel with
+ * w > 0) moves into a fresh table of 2^new_capacity_log2 records; on any failure the old table stays.  *n_dropped (nullable) =
+ * blocks left behind.  `who` names the entry in messages.  The caller has checked the capacity and flushed. */
+int gsdf_rebuild_impl(gsdf_ctx* c, int new_capacity_log2, bool skip_dead, long long* n_dropped, const char* who);
 void gsdf_enqueue_block_count(gsdf_ctx* c, unsigned int tag);   /* gsdf_merge.hip: existing blocks | tag << 32 -> pinned words progress[4..5] */
 
 inline int gsdf_fail(int code, const std::string& msg) {
@@ -245,6 +250,10 @@ struct gsdf_ctx {
     bool merged = false;                           /* gsdf_merge_allreduce has run: the map is the sum of all ranks (one-shot) */
     gsdf_dev<void> mx[GSDF_MX_BUFS];               /* scratch of the exchange (gsdf_merge.hip): grows, never shrinks */
     gsdf_posed_last posed_last;                    /* gsdf_merge_from_posed with this context as dst (gsdf_merge_posed.hip) */
+    /* the selection (gsdf_select.hip): one 64-bit word per block entry of the PRESENT table, bit = gsdf_block_local; allocated by
+     * the first select call, with a second bitmap of the same size behind it (the predicate set of the running call) */
+    gsdf_dev<unsigned long long> sel;
+    int sel_state = GSDF_SEL_NONE;                 /* none / valid / lost (a rehash moved the slots) */
     /* PhotoBA (PhotometricOptimizer) */
     int ba_n = 0;
     float ba_reg = 10.f;

@@ -37,6 +37,13 @@ GSDF_HD gsdf_v3 gsdf_matvec(const float* R, gsdf_v3 v) {       /* R row-major 3x
     r.z = gsdf_sum3(R[6] * v.x, R[7] * v.y, R[8] * v.z);
     return r;
 }
+/* p = R x + t as the tracker forms it (RigidPointOptimizer.cpp:70): the product rows as x0 + (x1 + x2), then + t per component.
+ * Shared by the registration passes, gsdf_align_residuals and gsdf_select_points. */
+GSDF_HD gsdf_v3 gsdf_rigid_apply(const float* R, gsdf_v3 t, gsdf_v3 x) {
+    const gsdf_v3 Rx = gsdf_matvec(R, x);
+    gsdf_v3 p = { Rx.x + t.x, Rx.y + t.y, Rx.z + t.z };
+    return p;
+}
 GSDF_HD gsdf_v3 gsdf_cross3(gsdf_v3 a, gsdf_v3 b) {             /* RigidPointOptimizer.cpp:78 */
     gsdf_v3 r;
     r.x = a.y * b.z - a.z * b.y;
@@ -107,6 +114,14 @@ GSDF_HD void gsdf_quat_to_R(const float* q /*x y z w*/, float* R) {
     R[0] = 1.f - (tyy + tzz); R[1] = txy - twz;         R[2] = txz + twy;
     R[3] = txy + twz;         R[4] = 1.f - (txx + tzz); R[5] = tyz - twx;
     R[6] = txz - twy;         R[7] = tyz + twx;         R[8] = 1.f - (txx + tyy);
+}
+
+/* the pose rule of gsdf_merge_from_posed and gsdf_select_points: seven finite values, | |q|^2 - 1 | <= 1e-4 (in double) */
+inline bool gsdf_pose7_ok(const float* pose7 /* tx ty tz qx qy qz qw */) {
+    for (int i = 0; i < 7; ++i) if (!isfinite(pose7[i])) return false;
+    const float* q = pose7 + 3;
+    const double n2 = (double)q[0] * q[0] + (double)q[1] * q[1] + (double)q[2] * q[2] + (double)q[3] * q[3];
+    return fabs(n2 - 1.0) <= 1e-4;
 }
 
 /* Eigen Quaternion(Matrix3) -- used by SE3(Matrix4f) (main_scan_3d.cpp:242,252) */

@@ -360,16 +360,23 @@ int merge_impl(gsdf_ctx* c, transport& tr, int64_t* n_blocks_out, int64_t* bytes
     return read_status(c);                                                                             /* (3) */
 }
 
-/* ---- growing the map (gsdf_grow): every block of the old table moves into a table of twice (or more) the entries ---- */
+/* ---- rebuilding the map (gsdf_grow, gsdf_compact): every block of the old table moves into a fresh table ---- */
 /* one wave per old entry: lane 0 claims the block's entry in the new key array, the 64 lanes copy its 64 records (and their
- * vis_ words); the new table is empty and larger, so the probe budget cannot run out */
+ * vis_ words); the new table is empty and the caller has seen to its room, so the probe budget cannot run out.
+ * dropped != nullptr is the "skip dead blocks" mode of gsdf_compact: a block none of whose 64 records has w > 0 stays behind
+ * and is counted there. */
 __global__ __launch_bounds__(256) void k_rehash(gsdf_table from, gsdf_table to, const uint32_t* vis_from, uint32_t* vis_to, int vw,
-                                                size_t n_blocks_from, gsdf_dev_state* st) {
+                                                size_t n_blocks_from, gsdf_dev_state* st, unsigned long long* dropped) {
     const size_t b = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= n_blocks_from) return;
     const int lane = threadIdx.x & 63;
     const unsigned long long bk = from.bkeys[b];
     if (bk == GSDF_KEY_EMPTY) return;
+    const size_t src = b * GSDF_BLOCK_VOX + lane;
+    if (dropped && !__ballot(from.vox[src].w > 0.f)) {
+        if (lane == 0) atomicAdd(dropped, 1ull);
+        return;
+    }
     int nb = -1;
     if (lane == 0) {
         const uint32_t h = gsdf_hash(bk) & to.block_mask;
@@ -378,7 +385,7 @@ __global__ __launch_bounds__(256) void k_rehash(gsdf_table from, gsdf_table to, 
     }
     nb = __shfl(nb, 0);
     if (nb < 0) return;
-    const size_t src = b * GSDF_BLOCK_VOX + lane, dst = (size_t)nb * GSDF_BLOCK_VOX + lane;
+    const size_t dst = (size_t)nb * GSDF_BLOCK_VOX + lane;
     const uint4* ps = reinterpret_cast<const uint4*>(from.vox + src);
     uint4* pd = reinterpret_cast<uint4*>(to.vox + dst);
     pd[0] = ps[0]; pd[1] = ps[1];
@@ -465,6 +472,13 @@ int gsdf_grow_impl(gsdf_ctx* c, int new_capacity_log2) {
         return gsdf_fail(GSDF_ERR_INVALID, "gsdf_grow: the new capacity_log2 must be larger than the present one and <= 30");
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = gsdf_flush_pending(c)) return rc;
+    return gsdf_rebuild_impl(c, new_capacity_log2, false, nullptr, "gsdf_grow");
+}
+
+/* The rebuild behind gsdf_grow and gsdf_compact: a fresh table, every block (skip_dead: every block that still holds a voxel)
+ * rehashed into it, then the context's table replaced.  Until that last step the old table is untouched. */
+int gsdf_rebuild_impl(gsdf_ctx* c, int new_capacity_log2, bool skip_dead, long long* n_dropped, const char* who_name) {
+    const std::string who = std::string(who_name) + ": ";
     HIP_TRY(hipStreamSynchronize(c->stream));
     const size_t n_new = (size_t)1 << new_capacity_log2;
     const int vw = c->map.vis ? c->vis_words : 0;
@@ -472,7 +486,7 @@ int gsdf_grow_impl(gsdf_ctx* c, int new_capacity_log2) {
     hipError_t e = nm.alloc(n_new, (size_t)vw);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        return gsdf_fail(GSDF_ERR_HIP, std::string("gsdf_grow: ") + hipGetErrorString(e));      /* the map is untouched */
+        return gsdf_fail(GSDF_ERR_HIP, who + hipGetErrorString(e));      /* the map is untouched */
     }
     const gsdf_table nt = nm.table(n_new);
     /* A sticky GSDF_STATUS_TABLE_FULL from an earlier fusion must not stop the map from growing: the rehash into an
@@ -482,7 +496,7 @@ int gsdf_grow_impl(gsdf_ctx* c, int new_capacity_log2) {
     auto bail = [&](hipError_t err, const char* what) {
         (void)hipStreamSynchronize(c->stream);                 /* nothing may still write into the new table, which goes with `nm` */
         (void)hipGetLastError();
-        return gsdf_fail(GSDF_ERR_HIP, std::string("gsdf_grow: ") + what + ": " + hipGetErrorString(err));
+        return gsdf_fail(GSDF_ERR_HIP, who + what + ": " + hipGetErrorString(err));
     };
     if ((e = hipMemcpy(&s0, c->st, sizeof(s0), hipMemcpyDeviceToHost)) != hipSuccess) return bail(e, "reading the status");
     const int full_before = s0.status & GSDF_STATUS_TABLE_FULL;
@@ -493,16 +507,28 @@ int gsdf_grow_impl(gsdf_ctx* c, int new_capacity_log2) {
     gsdf_launch_table_clear(c->stream, nt, n_new);
     if (vw && (e = hipMemsetAsync(nm.vis, 0, nm.vis.bytes(), c->stream)) != hipSuccess) return bail(e, "clearing vis_");
     const size_t nb_old = c->n_slots / GSDF_BLOCK_VOX;
-    hipLaunchKernelGGL(k_rehash, dim3((unsigned int)((nb_old + 3) / 4)), dim3(256), 0, c->stream, c->tab, nt, c->map.vis, nm.vis, vw, nb_old, c->st);
+    unsigned long long dropped = 0;
+    if (skip_dead && (e = hipMemsetAsync(c->counter, 0, sizeof(unsigned long long), c->stream)) != hipSuccess) return bail(e, "clearing the counter");
+    hipLaunchKernelGGL(k_rehash, dim3((unsigned int)((nb_old + 3) / 4)), dim3(256), 0, c->stream, c->tab, nt, c->map.vis, nm.vis, vw, nb_old, c->st,
+                       skip_dead ? c->counter.get() : nullptr);
     if ((e = hipGetLastError()) != hipSuccess) return bail(e, "launching the rehash");
+    if (skip_dead && (e = hipMemcpyAsync(&dropped, c->counter, sizeof(dropped), hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return bail(e, "reading the counter");
     if ((e = hipMemcpyAsync(&s1, c->st, sizeof(s1), hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return bail(e, "reading the status");
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return bail(e, "the rehash");
     if (full_before) {
         const int restored = s1.status | GSDF_STATUS_TABLE_FULL;
         (void)hipMemcpy(&c->st->status, &restored, sizeof(int), hipMemcpyHostToDevice);
     }
-    /* (cannot happen: the new table is empty and larger) */
-    if (s1.status & GSDF_STATUS_TABLE_FULL) return gsdf_fail(GSDF_ERR_TABLE_FULL, "gsdf_grow: the rehash ran out of probes");
+    /* The new table is empty and, for gsdf_grow, larger; gsdf_compact admits at most 45 % load: a probe chain of GSDF_MAX_PROBE
+     * entries that finds no room is out of practical reach.  Should it happen, the old table stays -- the map is unchanged -- and
+     * the bit the rehash raised is taken back unless an earlier fusion had set it. */
+    if (s1.status & GSDF_STATUS_TABLE_FULL) {
+        if (!full_before) {
+            const int cleared = s1.status & ~GSDF_STATUS_TABLE_FULL;
+            (void)hipMemcpy(&c->st->status, &cleared, sizeof(int), hipMemcpyHostToDevice);
+        }
+        return gsdf_fail(GSDF_ERR_TABLE_FULL, who + "the rehash ran out of probes; the map is unchanged");
+    }
     c->map = std::move(nm);                                    /* the old table is released here */
     c->tab = nt;
     c->n_slots = n_new; c->capacity_log2 = new_capacity_log2;
@@ -512,6 +538,10 @@ int gsdf_grow_impl(gsdf_ctx* c, int new_capacity_log2) {
     c->ba.mean.reset();
     c->ba_gate_fresh = false; c->ba_mean_valid = false;
     c->grow_forget = true;                                     /* auto-grow: the counts in flight describe the old table */
+    /* the selection names slots of the old table: lost (gsdf_select.hip); its bitmap is sized anew by the next select call */
+    if (c->sel_state == GSDF_SEL_VALID) c->sel_state = GSDF_SEL_LOST;
+    c->sel.reset();
+    if (n_dropped) *n_dropped = (long long)dropped;
     return GSDF_OK;
 }
 

@@ -146,12 +146,7 @@ struct stage_events {
     ~stage_events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
 };
 
-bool pose_ok(const float pose7[7]) {
-    for (int i = 0; i < 7; ++i) if (!std::isfinite(pose7[i])) return false;
-    const float* q = pose7 + 3;
-    const double n2 = (double)q[0] * q[0] + (double)q[1] * q[1] + (double)q[2] * q[2] + (double)q[3] * q[3];
-    return std::fabs(n2 - 1.0) <= 1e-4;
-}
+bool pose_ok(const float pose7[7]) { return gsdf_pose7_ok(pose7); }
 
 } // namespace
 

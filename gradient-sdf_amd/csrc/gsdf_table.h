@@ -26,6 +26,9 @@
  * (MapGradPixelSdf.cpp:108-109), weights are positive and only ever added, and records are zeroed by
  * the table clear.  The running mean of the reference (MapGradPixelSdf.cpp:111) equals s / w, so
  * storing the additive sums makes fusion order-free and shard-mergeable.
+ * Removal (gsdf_select.hip) keeps both invariants: gsdf_erase_selected zeroes whole records -- what the
+ * table clear leaves -- and never touches a block key, so entries are still never freed in place;
+ * gsdf_compact gives the entries of blocks without a voxel back by rebuilding the table (gsdf_grow's rehash).
  *
  * Why blocks: a camera tile touches ~1000 voxels per frame but only ~50 blocks and ~400 lines, so
  * the fusion flush and the tracker's gather move 2.6x fewer lines than with per-voxel hashing, the

@@ -145,6 +145,26 @@ bool MapGradPixelSdf::merge_from(const MapGradPixelSdf& other, const SE3& pose, 
     /* the pose goes as the 7 floats SE3 holds, like RigidPointOptimizer::optimize_points hands its pose_ to gsdf_align_points */
     return gsdf_merge_from_posed(ctx_, other.ctx_, pose.pose7(), n_voxels, n_blocks) == GSDF_OK;
 }
+/* removing voxels: the selection, erase, compact (include/gsdf.h; not in the reference) */
+bool MapGradPixelSdf::select_box(const Vec3f& lo, const Vec3f& hi, int op, int64_t* n) { return gsdf_select_box(ctx_, lo.data(), hi.data(), op, n) == GSDF_OK; }
+bool MapGradPixelSdf::select_weight(float w_min, float w_max, int op, int64_t* n) { return gsdf_select_weight(ctx_, w_min, w_max, op, n) == GSDF_OK; }
+bool MapGradPixelSdf::select_points(const std::vector<float>& pts3, float radius, const SE3* pose, int op, int64_t* n) {
+    return gsdf_select_points(ctx_, pts3.data(), (int64_t)(pts3.size() / 3), pose ? pose->pose7() : nullptr, radius, op, n) == GSDF_OK;
+}
+bool MapGradPixelSdf::select_invert(int64_t* n) { return gsdf_select_invert(ctx_, n) == GSDF_OK; }
+bool MapGradPixelSdf::select_clear() { return gsdf_select_clear(ctx_) == GSDF_OK; }
+bool MapGradPixelSdf::select_count(int64_t* n_voxels, int64_t* n_blocks) const { return gsdf_select_count(ctx_, n_voxels, n_blocks) == GSDF_OK; }
+bool MapGradPixelSdf::select_export(std::vector<int32_t>& keys, std::vector<float>& payload, bool raw_sums) const {
+    int64_t n = 0;
+    if (gsdf_select_export(ctx_, nullptr, nullptr, 0, &n, raw_sums ? 1 : 0) != GSDF_OK) return false;
+    keys.assign((size_t)n * 3, 0);
+    payload.assign((size_t)n * 5, 0.f);
+    return n == 0 || gsdf_select_export(ctx_, keys.data(), payload.data(), n, &n, raw_sums ? 1 : 0) == GSDF_OK;
+}
+bool MapGradPixelSdf::erase_selected(int64_t* n_voxels, int64_t* n_blocks_emptied) { return gsdf_erase_selected(ctx_, n_voxels, n_blocks_emptied) == GSDF_OK; }
+bool MapGradPixelSdf::compact(int new_capacity_log2, int64_t* n_blocks_dropped) { return gsdf_compact(ctx_, new_capacity_log2, n_blocks_dropped) == GSDF_OK; }
+bool MapGradPixelSdf::crop(const Vec3f& lo, const Vec3f& hi) { return select_box(lo, hi) && select_invert() && erase_selected() && compact(); }
+bool MapGradPixelSdf::prune(float min_weight) { return select_weight(0.f, min_weight) && erase_selected() && compact(); }
 bool MapGradPixelSdf::save_sdf(std::string filename) { return gsdf_exports::write_sdf_txt(ctx_, voxel_size_, filename); }
 bool MapGradPixelSdf::extract_mesh(std::string filename) { return gsdf_exports::write_mesh_ply(ctx_, voxel_size_, filename, nullptr); }
 bool MapGradPixelSdf::extract_mesh_indexed(std::string filename) { return gsdf_exports::write_indexed_mesh_ply(ctx_, filename, nullptr, nullptr); }

@@ -63,6 +63,25 @@ public:
      * when the library refuses (a MapPixelSdf on either side, enable_vis, different voxel size or truncation, no room) or reports
      * keys beyond the packable range (the rest is merged then); gsdf_last_error says which */
     bool merge_from(const MapGradPixelSdf& other, const SE3& pose, int64_t* n_voxels = nullptr, int64_t* n_blocks = nullptr);
+    /* Removing voxels (include/gsdf.h, "REMOVING VOXELS"; not in the reference, whose map only grows): the context's one
+     * selection -- select_box (closed box of voxel centres), select_weight (w_min <= w < w_max), select_points (centres within
+     * radius of a point; pose, nullable, moves the points first), each combined by op = GSDF_SEL_REPLACE / ADD / INTERSECT /
+     * SUBTRACT, select_invert, select_clear --, its consumers select_count and select_export (sorted (z, y, x), payload as
+     * export_arrays or raw sums), erase_selected (member records zeroed, block keys stay) and compact (the table rebuilt without
+     * its empty blocks; 0 keeps the capacity).  crop = box, invert, erase, compact; prune = weight [0, min_weight), erase,
+     * compact.  Nullable counts as in the C entries.  false when the library refuses (gsdf_last_error says why: a lost
+     * selection after the table grew, a NaN bound, a radius beyond 16 voxels, no room for compact).  MapPixelSdf inherits them */
+    bool select_box(const Vec3f& lo, const Vec3f& hi, int op = GSDF_SEL_REPLACE, int64_t* n = nullptr);
+    bool select_weight(float w_min, float w_max, int op = GSDF_SEL_REPLACE, int64_t* n = nullptr);
+    bool select_points(const std::vector<float>& pts3, float radius, const SE3* pose = nullptr, int op = GSDF_SEL_REPLACE, int64_t* n = nullptr);
+    bool select_invert(int64_t* n = nullptr);
+    bool select_clear();
+    bool select_count(int64_t* n_voxels, int64_t* n_blocks = nullptr) const;
+    bool select_export(std::vector<int32_t>& keys, std::vector<float>& payload, bool raw_sums = false) const;
+    bool erase_selected(int64_t* n_voxels = nullptr, int64_t* n_blocks_emptied = nullptr);
+    bool compact(int new_capacity_log2 = 0, int64_t* n_blocks_dropped = nullptr);
+    bool crop(const Vec3f& lo, const Vec3f& hi);
+    bool prune(float min_weight);
     bool save_sdf(std::string filename) override;                      /* MapGradPixelSdf.cpp:222-296 */
     bool extract_mesh(std::string filename) override;                  /* MapGradPixelSdf.cpp:124-175 */
     /* the same surface as an indexed mesh with a gradient normal per vertex, binary PLY (gsdf_extract_mesh_indexed; not in the

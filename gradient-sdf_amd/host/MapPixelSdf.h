@@ -25,7 +25,9 @@ public:
     bool extract_pc(std::string filename) override;                    /* MapPixelSdf.cpp:242-277 */
     bool save_sdf(std::string filename) override;                      /* MapPixelSdf.cpp:285-347 */
     /* extract_mesh, extract_mesh_indexed (plain and filtered), mesh_components and gradient_analysis: MapGradPixelSdf's (MapPixelSdf.cpp:192-240 runs the same marching
-     * cubes over the same dist values; the fusion stores the same gradient sums) */
+     * cubes over the same dist values; the fusion stores the same gradient sums).
+     * select_box / select_weight / select_points / select_invert / select_clear / select_count / select_export, erase_selected,
+     * compact, crop and prune: MapGradPixelSdf's as well (the selection reads keys and weights, which both map types store alike) */
 };
 
 #endif

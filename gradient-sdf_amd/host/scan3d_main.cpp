@@ -28,6 +28,11 @@
  *                     central / forward / backward gradient and the analytic one of the sphere scene in the file (rows
  *                     cx cy cz R), as count, mean, median, rmse and 95th percentile over |dist| < d for the ladder
  *                     d = 0.001 : 0.001 : trunc of matlab/GradientAnalysisSpheres.m (gsdf_gradient_stats);
+ *   --crop x0 y0 z0 x1 y1 z1
+ *                     after the last frame and before any export keep only the voxels whose centre lies in the closed box
+ *                     (metres; MapGradPixelSdf::crop = gsdf_select_box, invert, gsdf_erase_selected, gsdf_compact);
+ *   --prune-weight W  likewise drop the voxels of weight below W (MapGradPixelSdf::prune); with both, the crop comes first.
+ *                     Each prints `Voxels: N -> M`;
  * --scan-type grad-sdf (MapGradPixelSdf) or base-sdf (MapPixelSdf, the plain-SDF baseline, :99-114 / :226-233); base-sdf runs
  * on one GPU only (--gpus N > 1 refuses it).
  */
@@ -66,6 +71,9 @@ struct Options {
     int gpus = 1, rank = -1, decode_threads = 0;
     std::string transport = "rccl", rendezvous, gradient_spheres;
     long long mesh_min_faces = 0;        /* 0: no filtered mesh; GSDF_MESH_KEEP_LARGEST: --mesh-min-faces largest */
+    bool crop = false;
+    float crop_box[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };   /* --crop x0 y0 z0 x1 y1 z1 */
+    float prune_weight = -1.f;           /* --prune-weight W; < 0: off */
 };
 
 bool parse(int argc, char** argv, Options& o) {
@@ -79,9 +87,16 @@ bool parse(int argc, char** argv, Options& o) {
         if (a == "-h" || a == "--help") {
             std::cout << "Hash Table-Based 3D Scanning (MI355X)\n  --input --results --pose-file --first --last --scan-type"
                          " --data-type --voxel-size --trunc --save-sdf --width --height --hash-capacity --hash-max-capacity --device"
-                         " --sync --decode-threads --gpus --transport rccl|shm --mesh-indexed --mesh-min-faces <N|largest> --gradient-analysis <spheres.txt>\n"
+                         " --sync --decode-threads --gpus --transport rccl|shm --mesh-indexed --mesh-min-faces <N|largest> --gradient-analysis <spheres.txt>"
+                         " --crop x0 y0 z0 x1 y1 z1 --prune-weight W\n"
                          "  --scan-type grad-sdf|base-sdf (base-sdf: one GPU only, --gpus 1)\n";
             std::exit(0);
+        }
+        if (a == "--crop") {                                           /* six values */
+            if (i + 6 >= argc) { std::cerr << "--crop takes x0 y0 z0 x1 y1 z1" << std::endl; return false; }
+            for (int k = 0; k < 6; ++k) o.crop_box[k] = std::stof(argv[++i]);
+            o.crop = true;
+            continue;
         }
         if (!val(v)) { std::cerr << "missing value for " << a << std::endl; return false; }
         if (a == "--input") o.input = v;
@@ -104,6 +119,10 @@ bool parse(int argc, char** argv, Options& o) {
         else if (a == "--transport") o.transport = v;
         else if (a == "--decode-threads") o.decode_threads = std::stoi(v);
         else if (a == "--gradient-analysis") o.gradient_spheres = v;
+        else if (a == "--prune-weight") {
+            o.prune_weight = std::stof(v);
+            if (!(o.prune_weight >= 0.f)) { std::cerr << "--prune-weight takes a weight >= 0" << std::endl; return false; }
+        }
         else if (a == "--mesh-min-faces") {
             o.mesh_min_faces = v == "largest" ? (long long)GSDF_MESH_KEEP_LARGEST : std::atoll(v.c_str());
             if (v != "largest" && o.mesh_min_faces < 1) { std::cerr << "--mesh-min-faces takes a count >= 1 or `largest`" << std::endl; return false; }
@@ -454,6 +473,20 @@ int run(int, char**, Options& opt) {
     }
     if (!lead) return 0;
 
+    if (opt.crop || opt.prune_weight >= 0.f) {                          /* after the last frame, before any export */
+        T.tic();
+        const int64_t before = tSDF->size();
+        if (opt.crop && !tSDF->crop(Vec3f(opt.crop_box[0], opt.crop_box[1], opt.crop_box[2]), Vec3f(opt.crop_box[3], opt.crop_box[4], opt.crop_box[5]))) {
+            std::cerr << "--crop: " << gsdf_last_error() << std::endl;
+            return 1;
+        }
+        if (opt.prune_weight >= 0.f && !tSDF->prune(opt.prune_weight)) {
+            std::cerr << "--prune-weight: " << gsdf_last_error() << std::endl;
+            return 1;
+        }
+        std::cout << "Voxels: " << before << " -> " << tSDF->size() << std::endl;
+        T.toc("Remove voxels from the map");
+    }
     const std::string prefix = "gradient_sdf";
     T.tic();
     std::string filename = opt.output + prefix + "_mesh_final.ply";

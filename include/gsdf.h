@@ -640,6 +640,78 @@ int gsdf_align_residuals_dev(gsdf_ctx* c, const float* pts_dev, int64_t n, const
 int gsdf_surface_cloud(gsdf_ctx* c, float* rows6_host, int64_t max_n, int64_t* n);
 int gsdf_surface_cloud_dev(gsdf_ctx* c, float* rows6_dev, int64_t max_n, int64_t* n);
 
+/* REMOVING VOXELS: a selection on the device, its consumers, erase and compact.  The reference's map only grows (tsdf_ is never
+ * erased from); a multi-session engine needs the opposite as well: take out what moved between sessions before
+ * gsdf_merge_from_posed, drop speckle of weight below the extraction threshold, crop to a region, take a region out and put it
+ * back later (gsdf_select_export + gsdf_merge_raw).
+ *
+ * A context owns at most one selection S: a set of voxel SLOTS of the present table, one 64-bit word per block entry, bit =
+ * the voxel's index in its 4x4x4 block (8 B per block entry: 512 KB at 2^22 records; allocated by the first select call).
+ * Membership is by slot, whether or not the voxel exists; every consumer (count, export, erase) acts on the members with w > 0
+ * at the time it runs, and the *n a select call reports (nullable) is that count at its return.
+ * States: none, valid, lost.  gsdf_reset, gsdf_select_clear, gsdf_erase_selected and gsdf_compact leave none.  Any rehash leaves
+ * a valid selection lost, because slots move: gsdf_grow, auto-grow, and the grows inside gsdf_merge_from, gsdf_merge_from_posed
+ * and gsdf_merge_allreduce.  On a lost selection the consumers, gsdf_select_invert and the combining ops (ADD, INTERSECT,
+ * SUBTRACT) return GSDF_ERR_INVALID with a message that says so; GSDF_SEL_REPLACE and gsdf_select_clear start over.  On none the
+ * consumers report zero and GSDF_OK, and the combining ops start from the empty set.
+ * op: S := P (REPLACE), S | P (ADD), S & P (INTERSECT), S & ~P (SUBTRACT), P the call's predicate set.
+ *
+ * Predicates: float, without FMA, in the order written.
+ *   centre  of voxel index (i, j, k): c = (vs * (float)i, vs * (float)j, vs * (float)k)          -- step 1 of gsdf_merge_from_posed
+ *   box     member iff lo[a] <= c[a] && c[a] <= hi[a] on all three axes.  lo > hi on an axis: the empty set.  A NaN bound:
+ *           GSDF_ERR_INVALID; infinities are allowed.  The kernel reads block keys only, no voxel records.
+ *   weight  member iff w_min <= w && w < w_max, w the stored weight sum.  w_max = +inf is allowed; a NaN: GSDF_ERR_INVALID.
+ *   points  p = x when pose7 == NULL, else p = R x + t exactly as gsdf_align_points and gsdf_align_residuals form it (R = Eigen's
+ *           toRotationMatrix of the quaternion as it comes, rows as x0 + (x1 + x2), then + t).  A point with a component of p
+ *           that is not finite is skipped.  A voxel is a member iff for some point, with d = c - p per component,
+ *               dx * dx + (dy * dy + dz * dz) <= radius * radius              (one float product on the right)
+ *           The set is defined over ALL voxels of the map; the kernel enumerates, per point and axis, the integer range
+ *           [ceil((p - radius) / vs) - 1, floor((p + radius) / vs) + 1] taken in double -- one index wider on each side than exact
+ *           arithmetic needs --, tests the predicate above on every candidate and leaves out candidates beyond the packable
+ *           +-2^20 range before any packing (a point farther than 2^21 voxels from the origin on an axis has none).
+ *           GSDF_ERR_INVALID: a negative or non-finite radius, radius > 16 * vs (at most 35^3 candidates per point), a pose that
+ *           gsdf_merge_from_posed would refuse (not finite, | |q|^2 - 1 | > 1e-4), n_pts < 0, NULL points with n_pts > 0.
+ *           n_pts == 0 is the empty predicate set.  The _dev variant reads n_pts x 3 floats of
+ *           DEVICE memory in place.  Bits are set with integer atomic OR: the result is a set, nothing depends on an order.
+ * gsdf_select_invert complements S over the slots of existing blocks (on none: everything).
+ * gsdf_select_count: members with w > 0, and the blocks that hold at least one (either pointer may be NULL).
+ * gsdf_select_export: the members with w > 0 in (z, y, x) key order, payload as gsdf_export (raw_sums selects sums or means).
+ * Sizing conventions of gsdf_surface_cloud: *n is always reported; keys and payload NULL or max_n == 0 is the sizing call; a
+ * max_n below the count writes nothing and returns GSDF_ERR_INVALID with the need in *n.  gsdf_select_export_raw_dev writes each
+ * member exactly once, in no stated order, as raw sums into DEVICE buffers like gsdf_export_raw_dev.  vis_ words are NOT
+ * carried by either export: a region taken out and merged back comes back without them.
+ *
+ * gsdf_erase_selected zeroes all 32 bytes of every member record, and its vis_ words when gsdf_enable_vis is on: exactly what
+ * the table clear leaves, so a later fusion into that key starts from nothing.  Block keys STAY: the lookup's "an empty entry
+ * ends the chain" rule holds because no entry is ever emptied.  *n_voxels = members that existed, *n_blocks_emptied = blocks
+ * that lost at least one voxel and hold none afterwards (both nullable).  It allocates nothing, so it cannot fail half-way.
+ * PhotoBA's gate list and mean cache are dropped as gsdf_grow drops them; a ColorUpsampler snapshot is a copy and stays.
+ * gsdf_compact rebuilds the table without the blocks that hold no voxel with w > 0 -- the rebuild of gsdf_grow with dead blocks
+ * left behind.  new_capacity_log2 0 keeps the capacity; otherwise 10..30, smaller than the present one included, as long as the
+ * live blocks stay at or below 45 % of the new block entries (the room rule of gsdf_merge_from): beyond that
+ * GSDF_ERR_TABLE_FULL with the map unchanged.  A failed allocation leaves the map unchanged.  *n_blocks_dropped is nullable.
+ * The map's exported bytes (gsdf_export, gsdf_export_vis) are unchanged.
+ *
+ * All entries are synchronous and launch a waiting pipelined fusion first.  Pose, frame log, Sdf::counter_ and gsdf_stats are
+ * left as they are.  Both map types.  Not built: carrying vis_ through an export, erasing across ranks. */
+#define GSDF_SEL_REPLACE   0
+#define GSDF_SEL_ADD       1
+#define GSDF_SEL_INTERSECT 2
+#define GSDF_SEL_SUBTRACT  3
+int gsdf_select_box(gsdf_ctx* c, const float lo[3], const float hi[3], int op, int64_t* n);
+int gsdf_select_weight(gsdf_ctx* c, float w_min, float w_max, int op, int64_t* n);
+int gsdf_select_points(gsdf_ctx* c, const float* pts_host, int64_t n_pts, const float pose7[7] /* nullable */, float radius,
+                       int op, int64_t* n);
+int gsdf_select_points_dev(gsdf_ctx* c, const float* pts_dev, int64_t n_pts, const float pose7[7] /* nullable */, float radius,
+                           int op, int64_t* n);
+int gsdf_select_invert(gsdf_ctx* c, int64_t* n);
+int gsdf_select_clear(gsdf_ctx* c);
+int gsdf_select_count(gsdf_ctx* c, int64_t* n_voxels, int64_t* n_blocks);
+int gsdf_select_export(gsdf_ctx* c, int32_t* keys, float* payload, int64_t max_n, int64_t* n, int raw_sums);
+int gsdf_select_export_raw_dev(gsdf_ctx* c, int32_t* keys_dev, float* payload_raw_dev, int64_t max_n, int64_t* n);
+int gsdf_erase_selected(gsdf_ctx* c, int64_t* n_voxels, int64_t* n_blocks_emptied);
+int gsdf_compact(gsdf_ctx* c, int new_capacity_log2 /* 0 = keep */, int64_t* n_blocks_dropped);
+
 /* Voxel-hash raycaster: depth (camera z, 0 = no hit) and camera-frame normals (3 planes, nullable) of the
  * fused map seen from pose (R, t) through K.  Named in BASELINE.json's north_star but ABSENT from the
  * reference: it is defined on top of Sdf::weights / Sdf::tsdf (MapGradPixelSdf.h:109-125) and the

@@ -9,7 +9,9 @@ time of one batch of 5 pass + head pairs divided by 5 (conv_threshold = 0, so al
 k_track_pass's launches on map A for a frame of the stream.  One JSON line, also written to profiles/align_points.json (or --out).
 --merge goes on to the merge under the recovered pose instead (merge_main): profiles/merge_posed.json.
 --multi measures the multi-start registration instead (multi_main): profiles/align_multi.json.
---robust measures the registration with a robust loss beside the plain one (robust_main): profiles/align_robust.json."""
+--robust measures the registration with a robust loss beside the plain one (robust_main): profiles/align_robust.json.
+--erase-moved erases what moved between two sessions before merging them, and times the selection entries (erase_main):
+profiles/erase.json."""
 import argparse, json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -323,6 +325,138 @@ def robust_main(args):
     return 0
 
 
+def erase_main(args):
+    """--erase-moved: the scene of --robust (320x240 spheres, session B with its third sphere moved, B fused in a frame of its
+    own) taken to a merged map that holds the moved object once.  (1) B's surface cloud is registered against A with Tukey at
+    2 cm.  (2) gsdf_align_residuals of each map's cloud against the OTHER map: B's under the recovered pose, A's under its inverse.
+    (3) The points that hit and lie 2 cm or more off the other map are what moved.  (4) gsdf_select_points with radius = the
+    truncation distance on the map the points come from.  (5) Both maps erased, then gsdf_merge_from_posed.  Reports the triangle
+    and component counts of the merged map (gsdf_mesh_components) with and without the erase.  Then, on the bench-stream map
+    (S-tum 640x480, --frames frames, 1 cm voxels), the wall time of every new entry (median of --reps) beside gsdf_count, a
+    whole-table sweep; erase and compact run on a fresh copy of the map each time.  Nothing is gated.  One JSON line, also
+    written to profiles/erase.json (or --out)."""
+    import __graft_entry__ as graft
+    import align_points_ref as ref
+    pkg = graft.package()
+    B = pkg.binding
+    LOSS, SCALE = B.LOSS_TUKEY, np.float32(0.02)
+    W, H = 320, 240
+    kw = dict(n_frames=12, seed=1, step_deg=0.5)
+    sa, sb = pkg.synth.Sequence("spheres", W, H, **kw), pkg.synth.Sequence("spheres", W, H, **kw)
+    sb.spheres = np.array(sb.spheres, np.float64).copy()
+    sb.spheres[2, :3] += (0.04, -0.02, 0.012)
+    vs = np.float32(0.01); T = np.float32(10) * vs
+    new = lambda: pkg.GradSdf(vs, T, W, H, sa.K, capacity_log2=21)   # noqa: E731
+    a, b = new(), new()
+    _, Rd, td = ref.displace(np.zeros((1, 3)))
+    for i in range(8):
+        a.update(*sa.frame(i))
+    for i in range(4, 12):                              # B's own frame: x_b = Rd^T (x - td)
+        d, R, t = sb.frame(i)
+        b.update(d, (Rd.T @ np.asarray(R, np.float64).reshape(3, 3)).astype(np.float32), (Rd.T @ (np.asarray(t, np.float64) - td)).astype(np.float32))
+    cloud_a, cloud_b = a.surface_cloud()[:, :3].copy(), b.surface_cloud()[:, :3].copy()
+    conv, pose, passes, _ = a.align_points_robust(cloud_b, ref.IDENTITY, LOSS, SCALE)
+    Rg = quat_to_R(pose[3:])
+    inv = np.concatenate([-(Rg.T @ pose[:3].astype(np.float64)), [-pose[3], -pose[4], -pose[5], pose[6]]]).astype(np.float32)
+    phi_b, w_b = a.align_residuals(cloud_b, pose)
+    phi_a, w_a = b.align_residuals(cloud_a, inv)
+    off_b, off_a = (w_b > 0) & (np.abs(phi_b) >= SCALE), (w_a > 0) & (np.abs(phi_a) >= SCALE)
+
+    def copy_of(g):
+        c = new()
+        c.merge_from(g)
+        return c
+
+    def merged(erase):
+        a2, b2 = copy_of(a), copy_of(b)
+        info = {}
+        if erase:
+            na = a2.select_points(cloud_a[off_a], T)
+            nb = b2.select_points(cloud_b[off_b], T)
+            info = {"selected_in_a": int(na), "selected_in_b": int(nb), "erased_in_a": list(a2.erase_selected()), "erased_in_b": list(b2.erase_selected())}
+        nv, nbk = a2.merge_from_posed(b2, pose)
+        _, fc, counts, _ = a2.mesh_components()
+        info.update({"merge_n_voxels": int(nv), "merge_n_blocks": int(nbk), "voxels": a2.count(), "triangles": int(len(fc)), "components": int(len(counts)),
+                     "components_of_100_faces_or_more": int((counts[:, 0] >= 100).sum()) if len(counts) else 0})
+        a2.close(); b2.close()
+        return info
+    demo = {"scene": "spheres %dx%d, A = frames 0..7, B = frames 4..11 in a frame of its own with sphere 2 moved by (0.04, -0.02, 0.012) m, voxel %.3g m" % (W, H, float(vs)),
+            "registration": {"loss": "TUKEY", "scale_m": float(SCALE), "converged": bool(conv), "passes": int(passes),
+                             "rotation_error_deg": round(float(np.rad2deg(np.arccos(np.clip((np.trace(Rg.T @ Rd) - 1) / 2, -1, 1)))), 4),
+                             "translation_error_mm": round(1e3 * float(np.abs(pose[:3].astype(np.float64) - td).max()), 3)},
+            "cloud_points": {"a": int(len(cloud_a)), "b": int(len(cloud_b))},
+            "hit_and_2cm_or_more_off_the_other_map": {"a": int(off_a.sum()), "b": int(off_b.sum())},
+            "select_radius_m": float(T), "merged_without_erase": merged(False), "merged_with_erase": merged(True)}
+    a.close(); b.close()
+
+    # the time of every new entry on the bench map, beside gsdf_count
+    W, H, n = 640, 480, args.frames
+    seq = pkg.synth.Sequence("tum", W, H, n_frames=n, seed=0)
+    g = pkg.GradSdf(vs, T, W, H, seq.K, capacity_log2=22)
+    for i in range(n):
+        g.update(*seq.frame(i))
+    keys, _ = g.export()
+    cloud = g.surface_cloud()[:, :3].copy()
+    pts = cloud[::max(1, len(cloud) // 20000)]
+    dev = g.upload(pts)
+    nvox = g.count()
+    mid = (vs * np.median(keys, axis=0)).astype(np.float32)
+    lo, hi = mid - np.float32(0.5), mid + np.float32(0.5)
+    kd, pd = g.upload(np.zeros((nvox, 3), np.int32)), g.upload(np.zeros((nvox, 5), np.float32))
+
+    def timed(fn, reps=args.reps):
+        fn()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter(); r = fn(); ts.append(time.perf_counter() - t0)
+        return round(float(np.median(ts)) * 1e3, 3), r
+    tm = {}
+    tm["gsdf_count"], _ = timed(g.count)
+    tm["gsdf_select_box"], n_box = timed(lambda: g.select_box(lo, hi))
+    tm["gsdf_select_weight"], n_w = timed(lambda: g.select_weight(0, 5))
+    tm["gsdf_select_points"], n_p = timed(lambda: g.select_points(pts, T))
+    tm["gsdf_select_points_dev"], _ = timed(lambda: g.select_points_dev(dev, len(pts), T))
+    tm["gsdf_select_points_dev_radius_2_voxels"], n_p2 = timed(lambda: g.select_points_dev(dev, len(pts), np.float32(2) * vs))
+    tm["gsdf_select_invert"], _ = timed(g.select_invert)
+    g.select_box(lo, hi)
+    tm["gsdf_select_count"], _ = timed(g.select_count)
+    tm["gsdf_select_export"], _ = timed(lambda: g.select_export(raw=True))
+    tm["gsdf_select_export_raw_dev"], _ = timed(lambda: g.select_export_raw_dev(kd.value, pd.value, nvox))
+    tm["gsdf_select_clear"], _ = timed(g.select_clear)
+    te, tc, tcs, counts = [], [], [], None
+    inside = ((vs * keys.astype(np.float32) >= lo) & (vs * keys.astype(np.float32) <= hi)).all(axis=1)
+    live = int(len(np.unique(keys[inside] >> 2, axis=0)))   # blocks the crop keeps; the smallest capacity the 45 % rule admits for them
+    small = 10
+    while live * 100 > ((1 << small) // 64) * 45:
+        small += 1
+    for _ in range(args.reps + 1):                      # the first one warm; each on a fresh copy of the map
+        c = pkg.GradSdf(vs, T, W, H, seq.K, capacity_log2=22)
+        c.merge_from(g)
+        c.select_box(lo, hi)
+        c.select_invert()
+        t0 = time.perf_counter(); ev = c.erase_selected(); te.append(time.perf_counter() - t0)
+        t0 = time.perf_counter(); dropped = c.compact(); tc.append(time.perf_counter() - t0)
+        t0 = time.perf_counter(); c.compact(small); tcs.append(time.perf_counter() - t0)
+        counts = {"erased_voxels": int(ev[0]), "blocks_emptied": int(ev[1]), "blocks_dropped": int(dropped), "voxels_left": c.count(),
+                  "live_blocks": live, "smallest_capacity_log2_admitted": small}
+        c.close()
+    tm["gsdf_erase_selected"] = round(float(np.median(te[1:])) * 1e3, 3)
+    tm["gsdf_compact_same_capacity"] = round(float(np.median(tc[1:])) * 1e3, 3)
+    tm["gsdf_compact_to_the_smallest_capacity_after_it"] = round(float(np.median(tcs[1:])) * 1e3, 3)
+    bench = {"map": "S-tum %dx%d, %d frames, voxel %.3g m, capacity 2^22" % (W, H, n, float(vs)), "voxels": int(nvox),
+             "blocks": int(len(np.unique(keys >> 2, axis=0))), "reps": args.reps, "points": int(len(pts)), "select_radius_m": float(T),
+             "selected": {"box_1m": int(n_box), "weight_0_5": int(n_w), "points_radius_T": int(n_p), "points_radius_2_voxels": int(n_p2)},
+             "crop_to_the_box": counts, "wall_ms": tm,
+             "note": "wall time of the synchronous call from Python, median of reps after one warm call; gsdf_count is the whole-table sweep the engine already had"}
+    g.close()
+    out = {"erase_moved": demo, "bench_map": bench}
+    line = json.dumps(out)
+    print(line)
+    with open(args.out, "w") as f:
+        f.write(line + "\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=64)
@@ -330,11 +464,14 @@ def main():
     ap.add_argument("--merge", action="store_true", help="also merge B into A under the recovered pose (gsdf_merge_from_posed); writes profiles/merge_posed.json")
     ap.add_argument("--multi", action="store_true", help="multi-start registration (gsdf_align_points_multi) against sequential single calls, and the basin sweep; writes profiles/align_multi.json")
     ap.add_argument("--robust", action="store_true", help="robust registration (gsdf_align_points_robust, Tukey at 2 cm) beside the plain one on a scene with a moved object, residual counts and timings; writes profiles/align_robust.json")
+    ap.add_argument("--erase-moved", action="store_true", help="erase what moved between the two sessions of the --robust scene before merging them (gsdf_select_points, gsdf_erase_selected), and time the selection entries on the bench map; writes profiles/erase.json")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", "merge_posed.json" if args.merge else "align_multi.json" if args.multi else
-                                "align_robust.json" if args.robust else "align_points.json")
+                                "align_robust.json" if args.robust else "erase.json" if args.erase_moved else "align_points.json")
+    if args.erase_moved:
+        return erase_main(args)
     if args.merge:
         return merge_main(args)
     if args.multi:
